@@ -13,7 +13,9 @@ sharded over the ranks (global sample index keys the dropout masks, so the resul
 depend on N), each rank recomputes the sample-invariant prefix, one all-reduce(SUM) of the
 15x352x1024 fp32 probability sums per frame.  T is fixed -> "scaling": "strong".
 
-Prints ONE JSON line (rank 0).  `roofline`: the dominant kernel (the MFMA kernel with the
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps frames and reports
+them (`value` frames/s, `ms_per_step`); everything else is measured only with --full:
+`roofline`: the dominant kernel (the MFMA kernel with the
 largest share of GPU time): executed matrix-core FLOP/s from HIP events on its launch stream
 during the timed region against the dense peak of the instruction type it issues (frac <= 1),
 with the algorithmic (direct-convolution) rate beside it and the whole-frame matrix-core
@@ -22,6 +24,11 @@ utilisation.  At N = 1 the line also carries `configs` (BASELINE configs[1], [3]
 reference's segmentImage boundary, PCIe included).  `cpu_baseline`: this repo's CPU oracle
 (a restatement of the reference path — not Caffe/cuDNN/OpenCV, which are unavailable)
 timed on the host cores for a bounded sample and extrapolated to the same frame.
+
+--dump-outputs DIR: after the timed frames, what the LAST of them computed (the maps, rank 0's
+keys, descriptors, stereo matches and entropy-gate selection) as DIR/<name>.npy in float32 /
+float64.  The inputs, weights and frame seeds are fixed, so two builds can be compared output
+for output.
 """
 import argparse
 import json
@@ -331,11 +338,12 @@ def membound_block(prof, fp, d_left, H, W, T, classes):
     return rows
 
 
-def time_segnet(sn, frame, steps, warmup, barrier, profile_every=8, events=True, flush=lambda: None):
+def time_segnet(sn, frame, steps, warmup, barrier, profile_every=8, events=True, flush=lambda: None, detail=True, after_timed=lambda: None):
     """Warm up, time `steps` calls of frame(seed) between barriers, return (elapsed s, MFMA-kernel rows of the timed region — a pair:
     the frames profiled in one lane, the frames profiled with their lanes kept —, all-kernel rows of min(steps, 10) further untimed
     single-lane frames).  Inside the timed region frame i carries events when i % profile_every is 0 (issued in ONE lane: a launch has
-    the GPU to itself) or profile_every / 2 (lanes kept: the kernel's time while it shares the chip with the other sample group)."""
+    the GPU to itself) or profile_every / 2 (lanes kept: the kernel's time while it shares the chip with the other sample group).
+    after_timed() runs right after the timed region, before any further frame; detail=False: no untimed frames (rows None, count 0)."""
     for i in range(warmup):
         frame(1000 + i)
     flush()
@@ -371,6 +379,9 @@ def time_segnet(sn, frame, steps, warmup, barrier, profile_every=8, events=True,
         elif last in (half, half + 1):
             two_lane += sn.profile_read()
     prof_timed = (one_lane, two_lane)
+    after_timed()
+    if not detail:
+        return elapsed, prof_timed, None, 0
     n_detail = min(steps, 10)
     sn.profile(True, reset=True)
     for i in range(n_detail):
@@ -481,6 +492,20 @@ def tracking_config(last, fp, intr, device, reps=20):
                       "tests/test_pin_optimizer.py (22 cases against the reference's Optimizer.cc compiled untouched), tests/test_gpu_ba_solve.py (1e-7 vs the oracle)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(directory, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 only, at most DUMP_LIMIT_BYTES in all)."""
+    assert outputs, "no outputs were captured from the timed frames"
+    assert all(a.dtype in (np.float32, np.float64) for a in outputs.values())
+    total = sum(a.nbytes for a in outputs.values())
+    assert total <= DUMP_LIMIT_BYTES, f"{total} bytes of outputs"
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def launch_command(argv, n, port=None):
     """The command `python bench.py --gpus N ...` re-executes itself as when it was started plainly (no torch.distributed.run around it):
     one rank per GPU of this node, rendezvous on 127.0.0.1 (the container's hostname may not resolve)."""
@@ -503,12 +528,20 @@ def main():
     ap.add_argument("--height", type=int, default=352)
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--no-orb", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--serial", action="store_true", help="N = 1: one frame in flight (the host tail of a frame is not overlapped with the next frame's device work)")
-    ap.add_argument("--configs", default="all", help="N = 1 only: which further BASELINE configs to measure after the main one and "
-                    "report under \"configs\": all | none | comma list of basic,t48,ba,host,track,shards (rocprofv3 runs use one at a time)")
-    ap.add_argument("--per-layer", action="store_true", help="print the per-layer event timings to stderr")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, measure everything else: roofline and per-kernel figures (untimed "
+                    "profiled frames), the pipeline self-check and serial_fps, membound, the further configs and the CPU baseline")
+    ap.add_argument("--configs", default=None, help="--full, N = 1 only: which further BASELINE configs to measure after the main one and "
+                    "report under \"configs\": all (default) | none | comma list of basic,t48,ba,host,track,shards (rocprofv3 runs use one at a time)")
+    ap.add_argument("--per-layer", action="store_true", help="--full: print the per-layer event timings to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed frame computed to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.per_layer or args.configs not in (None, "none")):
+        ap.error("--configs and --per-layer report what only a --full run measures: add --full")
+    args.configs = args.configs or "all"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # started plainly (`python bench.py --gpus N`): become the launcher of N ranks; rank 0 prints the one JSON line to this stdout
         cmd = launch_command(sys.argv[1:], args.gpus)
@@ -723,6 +756,7 @@ def main():
             tail_probe.append(time.perf_counter() - t0)
         stats["kps"], stats["matches"] = r["semantic_keys"], r["stereo_matches"]
         stats["last"] = r
+        stats["last_slot"], stats["last_selected"] = slot, acc          # (--dump-outputs: the maps of this frame stay in that slot until it is reused)
         if keep is not None:            # (the self-check below: a frame's maps, keys, matches and selection by seed)
             keep[seed] = (maps_s[slot][0].clone(), maps_s[slot][1].clone(), maps_s[slot][2].clone(), r["keys"].copy(), r["right"].copy(), r["depth"].copy(), acc.copy())
 
@@ -756,11 +790,32 @@ def main():
 
     # Every 8th timed frame carries HIP events around its MFMA kernels (that is what `roofline` is measured on; those frames
     # issue the forward in one lane so that a launch has the GPU to itself); SIVO_BENCH_NO_EVENTS=1: none at all.
+    # A plain run keeps them too: its timed frames are the same program as those of a --full run, so both report the same `value`.
     PROFILE_EVERY = 8
     events = os.environ.get("SIVO_BENCH_NO_EVENTS") != "1"
-    elapsed, prof_timed, prof, n_detail = time_segnet(sn, frame, args.steps, args.warmup, barrier, PROFILE_EVERY, events, flush)
+    outputs = {}
+
+    def capture():
+        """--dump-outputs: what the last timed frame returned to its caller, copied to the host before any further frame runs."""
+        if args.dump_outputs is None or rank != 0:
+            return
+        m = maps_s[stats["last_slot"]] if do_orb else maps
+        outputs["classes"] = m[0].cpu().numpy().astype(np.float32)
+        outputs["confidence"] = m[1].cpu().numpy().astype(np.float64)
+        outputs["entropy"] = m[2].cpu().numpy().astype(np.float64)
+        if do_orb:
+            r = stats["last"]
+            k = r["keys"]
+            outputs["keys"] = np.stack([k[f].astype(np.float64) for f in k.dtype.names], 1)          # (x, y, size, angle, response, octave, class_id)
+            outputs["descriptors"] = r["desc"].astype(np.float32)
+            outputs["right"] = r["right"].astype(np.float32)
+            outputs["depth"] = r["depth"].astype(np.float32)
+            outputs["selected"] = np.asarray(stats["last_selected"]).astype(np.float32)
+
+    elapsed, prof_timed, prof, n_detail = time_segnet(sn, frame, args.steps, args.warmup, barrier, PROFILE_EVERY, events, flush,
+                                                      detail=args.full, after_timed=capture)
     pipeline_check = None
-    if pipelined and world == 1:
+    if args.full and pipelined and world == 1:
         # self-check of the two-frames-in-flight loop: the frame with seed 777 between two others, against the same frame alone
         keep = {}
         for sd in (776, 777, 778):
@@ -775,7 +830,7 @@ def main():
         keep = None
         pipeline_check = bool(all(torch.equal(x, y) if torch.is_tensor(x) else np.array_equal(x, y) for x, y in zip(two, one)))
     serial_fps = None
-    if pipelined and world == 1:              # the same loop with one frame in flight, for the record
+    if args.full and pipelined and world == 1:              # the same loop with one frame in flight, for the record
         slots = 1
         barrier()
         t0 = time.perf_counter()
@@ -823,9 +878,11 @@ def main():
     if rank == 0 and tail_probe:
         print(f"host tail (semantic filter + median cull) mean {1e3 * float(np.mean(tail_probe)):.3f} ms over {len(tail_probe)} frames", file=sys.stderr)
     if rank == 0:
+        if args.dump_outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         fps = args.steps / elapsed
         ms_frame = 1e3 * elapsed / args.steps
-        if args.per_layer:
+        if args.full and args.per_layer:
             for p in prof:
                 ms = p["ms_total"] / max(p["launches"], 1)
                 if not p["launches"]:
@@ -841,7 +898,6 @@ def main():
                 "f16x3 kernel all of them; each fp32 product is three fp16 MFMA products — so executed = 3/4 of algorithmic for the GEMM and 3x for the direct "
                 "kernel).  mfma_kernels lists every matrix-core kernel of the frame with the same figures: the two f16x3 kernels take about the same time, and "
                 "which of them is 'dominant' can change from run to run")
-        roofline = mfma_roofline(prof_timed, prof, n_timed, n_detail, ms_frame, note)
         out = {"metric": "frames/sec, SIVO per-frame path (ORB+SegNet T=%d+entropy) %dx%d" % (T, H, W),
                "value": round(fps, 4), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(ms_frame, 3), "higher_is_better": True, "scaling": "strong",
@@ -857,8 +913,6 @@ def main():
                           "pipeline": ("a frame's host tail (semantic filter, median cull, entropy gate) runs while the NEXT frame's device work is already enqueued; "
                                        "every frame's results are those of the serial loop (tests/test_gpu_frame_e2e.py), latency + 1 frame; serial_fps = the same loop with one frame in flight")
                                       if pipelined else None,
-                          "serial_fps": round(serial_fps, 4) if serial_fps else None,
-                          "pipelined_frame_equals_serial_frame": pipeline_check,      # maps (u8 / f64 / f64), keys, mvuRight, mvDepth, selection: bit for bit
                           "orb": bool(do_orb), "semantic_keys": stats["kps"], "stereo_matches": stats["matches"],
                           "entropy_gate": ({"in_timed_frame": True, "keys_selected": stats["selected"], "threshold_bits": GATE_TH,
                                             "ms_per_call": round(1e3 * stats["gate_s"] / max(stats["gate_n"], 1), 4),
@@ -869,16 +923,18 @@ def main():
                           "gemm": dict(zip(("mode", "fp16_overflow_frames"), sn.gemm_status()[:2]), frames_recomputed=stats["recomputed"]),
                           "accuracy_guard": guard_summary,
                           "parity": "tests/test_gpu_frame_e2e.py (this frame end to end against the oracle pipeline), tests/test_gpu_segnet_fullsize.py (this network "
-                                    "configuration, every logit, oracle-checked), tests/test_gpu_orb.py, tests/test_gpu_match_ba.py"},
-               "roofline": roofline}
-
-        if world == 1:
-            out["membound"] = membound_block(prof, fp, d_left, H, W, T, sn.classes)
+                                    "configuration, every logit, oracle-checked), tests/test_gpu_orb.py, tests/test_gpu_match_ba.py"}}
+        if args.full:
+            out["config"]["serial_fps"] = round(serial_fps, 4) if serial_fps else None
+            out["config"]["pipelined_frame_equals_serial_frame"] = pipeline_check     # maps (u8 / f64 / f64), keys, mvuRight, mvDepth, selection: bit for bit
+            out["roofline"] = mfma_roofline(prof_timed, prof, n_timed, n_detail, ms_frame, note)
+            if world == 1:
+                out["membound"] = membound_block(prof, fp, d_left, H, W, T, sn.classes)
         if multi:
             out["multi_gpu"] = multi
 
     # ------------------------------------------------------------------------------------------ further configs (N = 1)
-    want = set() if (world > 1 or args.configs == "none") else set(("basic,t48,ba,host,track,shards" if args.configs == "all" else args.configs).split(","))
+    want = set() if (not args.full or world > 1 or args.configs == "none") else set(("basic,t48,ba,host,track,shards" if args.configs == "all" else args.configs).split(","))
     extra = []
     if rank == 0 and want:
         if "host" in want:
@@ -1039,7 +1095,7 @@ def main():
     if rank == 0:
         if extra:
             out["configs"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.net, T, H, W, text, w, bgr, left, right, "")
         print(json.dumps(out))
     if world > 1:

@@ -35,13 +35,24 @@ def oracle():
     return O
 
 
+KITTI_FRAME = os.path.join(ROOT, "tests", "golden", "frame_bgr_352x1024.npz")
+
+
+def load_kitti_frame():
+    """The committed 352x1024 BGR u8 crop (stored compressed, array "frame"), or None when the fixture is absent."""
+    if not os.path.exists(KITTI_FRAME):
+        return None
+    with np.load(KITTI_FRAME) as z:
+        return z["frame"]
+
+
 @pytest.fixture(scope="session")
 def kitti_like_bgr():
     """1024x352 BGR test frame: the committed crop of the reference's tests/data/test_image.png
     (tests/golden/make_golden.py), or a seeded synthetic frame when the fixture is absent."""
-    p = os.path.join(ROOT, "tests", "golden", "frame_bgr_352x1024.npy")
-    if os.path.exists(p):
-        return np.load(p)
+    frame = load_kitti_frame()
+    if frame is not None:
+        return frame
     return synthetic_frame(1234)[..., None].repeat(3, axis=2)
 
 

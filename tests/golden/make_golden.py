@@ -2,10 +2,10 @@
 """Regenerates the committed fixtures under tests/golden/ (run in the build container,
 where /root/reference exists; the GPU box only reads the committed files).
 
-frame_bgr_352x1024.npy   the reference's only real fixture, tests/data/test_image.png
+frame_bgr_352x1024.npz   the reference's only real fixture, tests/data/test_image.png
                          (1242x375 KITTI frame), centre-cropped to the network geometry
                          by the rule of src/orbslam/System.cc:161-163 (x0 = 109, y0 = 11),
-                         stored BGR as cv::imread would deliver it.
+                         stored BGR as cv::imread would deliver it (compressed, array "frame").
 netgraph_{standard,basic}.json  layer graphs parsed from the reference prototxts; tests
                          check that sivo_amd.netspec generates the same graphs.
 orb_kitti_golden.npz     oracle ORB output on that frame (keypoints + descriptors), frozen so
@@ -30,7 +30,7 @@ def main():
     assert im.shape == (375, 1242, 3)
     x0, y0 = 1242 // 2 - 1024 // 2, 375 // 2 - 352 // 2
     bgr = np.ascontiguousarray(im[y0:y0 + 352, x0:x0 + 1024, ::-1])
-    np.save(f"{HERE}/frame_bgr_352x1024.npy", bgr)
+    np.savez_compressed(f"{HERE}/frame_bgr_352x1024.npz", frame=bgr)
 
     keys = ("name", "type", "bottom", "top", "num_output", "pad", "kernel_size", "pool", "stride", "scale",
             "dropout_ratio", "sample_weights_test", "local_size", "alpha", "beta", "bn_mode")

@@ -35,14 +35,14 @@ class _Out(C.Structure):
 
 def scenes():
     """name -> (left, right, classes, extractor config)."""
-    from conftest import synthetic_stereo
+    from conftest import load_kitti_frame, synthetic_stereo
     out = {}
     for seed, disp in ((7, 8), (21, 23)):
         left, right = synthetic_stereo(seed, disparity=disp)
         out[f"synthetic-{seed}-d{disp}"] = (left, right)
-    p = os.path.join(ROOT, "tests", "golden", "frame_bgr_352x1024.npy")
-    if os.path.exists(p):
-        g = np.ascontiguousarray(np.load(p)[..., 0])
+    frame = load_kitti_frame()
+    if frame is not None:
+        g = np.ascontiguousarray(frame[..., 0])
         rng = np.random.default_rng(3)
         right = np.concatenate([g[:, 12:], np.repeat(g[:, -1:], 12, axis=1)], axis=1).astype(np.float64) + rng.normal(0, 1.5, g.shape)
         out["kitti-crop-d12"] = (g, np.clip(np.rint(right), 0, 255).astype(np.uint8))

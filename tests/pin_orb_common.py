@@ -16,12 +16,11 @@ KP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32),
 
 
 def images():
-    from conftest import synthetic_frame
+    from conftest import load_kitti_frame, synthetic_frame
     out = {"synthetic-7": synthetic_frame(7), "synthetic-21": synthetic_frame(21), "small-120x160": synthetic_frame(3, 120, 160),
            "odd-241x517": synthetic_frame(5, 241, 517)}
-    p = os.path.join(ROOT, "tests", "golden", "frame_bgr_352x1024.npy")
-    if os.path.exists(p):
-        frame = np.load(p)
+    frame = load_kitti_frame()
+    if frame is not None:
         out["kitti-crop"] = np.ascontiguousarray(frame[..., 0])
         out["kitti-crop-green"] = np.ascontiguousarray(frame[..., 1])
     rng = np.random.default_rng(11)

@@ -13,7 +13,7 @@ T, H, W = 2, 352, 1024
 text = netspec.basic_prototxt(T, H, W) if kind == "basic" else netspec.standard_prototxt(T, H, W)
 net = oproto.parse(text); w = wts.synth_weights(net["layers"], 42)
 sn = BayesianSegNet(prototxt=text, weights=wts.pack(net["layers"], w), T=T)
-img = np.load(os.path.join(ROOT, "tests/golden/frame_bgr_352x1024.npy"))[:H, :W].copy()
+img = np.load(os.path.join(ROOT, "tests/golden/frame_bgr_352x1024.npz"))["frame"][:H, :W].copy()
 ob = oracle.run_net(net, w, oracle.preprocess(img, T, H, W), SEED)
 _, logits, _ = sn.forward(torch.from_numpy(img).cuda(), SEED, want_logits=True)
 torch.cuda.synchronize()

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 export SIVO_BENCH_NO_EVENTS=1
 run() {  # label, dir, env..
   local label=$1 dir=$2; shift 2
-  (cd $dir && env "$@" timeout 300 python bench.py --configs none --no-cpu-baseline --steps 60 2>/dev/null) | python -c "
+  (cd $dir && env "$@" timeout 300 python bench.py --full --configs none --no-cpu-baseline --steps 60 2>/dev/null) | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$label', d['value'], 'fps', d['ms_per_step'], 'ms; serial', d['config']['serial_fps'])"

@@ -10,7 +10,7 @@ mkdir -p $O
 cd $R
 bench() {   # name, env...
   local name=$1; shift
-  env "$@" timeout 300 python bench.py --per-layer --configs none --no-cpu-baseline --steps 20 > $O/bench_$name.json 2> $O/bench_$name.err
+  env "$@" timeout 300 python bench.py --full --per-layer --configs none --no-cpu-baseline --steps 20 > $O/bench_$name.json 2> $O/bench_$name.err
   echo "bench $name rc=$?"; python - <<PY
 import json
 try:
@@ -34,7 +34,7 @@ for step in "$@"; do
     e2e) timeout 600 python -m pytest tests/test_gpu_frame_e2e.py -q -s > $O/e2e.log 2>&1; echo "e2e rc=$?"; grep -E "e2e|passed|failed|Error" $O/e2e.log | tail -8;;
     fullsize) timeout 1500 python -m pytest tests/test_gpu_segnet_fullsize.py -q -s > $O/fullsize.log 2>&1; echo "fullsize rc=$?"; grep -E "dlogit|passed|failed|FAILED|Error" $O/fullsize.log | tail -40;;
     track) timeout 900 python -m pytest tests/test_gpu_ba_solve.py tests/test_gpu_search.py tests/test_gpu_match_ba.py tests/test_pin_matcher.py tests/test_pin_optimizer.py tests/test_cpp_api.py tests/test_pin_helpers.py -m gpu -q -s > $O/track.log 2>&1; echo "track rc=$?"; grep -E "pose_optimize|passed|failed|FAILED|Error|FAIL " $O/track.log | tail -30;;
-    benchtrack) timeout 600 python bench.py --configs track,ba,shards --no-cpu-baseline --steps 20 > $O/bench_track.json 2> $O/bench_track.err; echo "benchtrack rc=$?"; tail -5 $O/bench_track.err; python - <<PY
+    benchtrack) timeout 600 python bench.py --full --configs track,ba,shards --no-cpu-baseline --steps 20 > $O/bench_track.json 2> $O/bench_track.err; echo "benchtrack rc=$?"; tail -5 $O/bench_track.err; python - <<PY
 import json
 try:
     d=json.load(open("$O/bench_track.json"))
@@ -49,7 +49,7 @@ PY
         timeout 120 python tools/ba_probe.py 30 2>/dev/null | tee $O/ba_probe.log
         rm -rf /tmp/prof_ba; (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_ba -o ba -- python $R/tools/ba_probe.py 10 > /dev/null 2>&1)
         f=$(find /tmp/prof_ba -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/kernel_stats_ba.csv && head -14 $O/kernel_stats_ba.csv | cut -c1-170
-        timeout 300 python bench.py --configs ba --no-cpu-baseline --no-orb --steps 3 --warmup 1 > $O/bench_ba.json 2> $O/bench_ba.err; python - <<PY
+        timeout 300 python bench.py --full --configs ba --no-cpu-baseline --no-orb --steps 3 --warmup 1 > $O/bench_ba.json 2> $O/bench_ba.err; python - <<PY
 import json
 try:
     d=json.load(open("$O/bench_ba.json"))

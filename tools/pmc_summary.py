@@ -2,7 +2,7 @@
 """Summarise rocprofv3 --pmc passes into per-kernel, per-dispatch figures.
 
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_f -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-orb
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_f -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-orb
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_w -- python bench.py ... (same)
   rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d /tmp/pmc_m -- ...
   python tools/pmc_summary.py out.json /tmp/pmc_f /tmp/pmc_w /tmp/pmc_m

@@ -24,7 +24,7 @@ pmc() {   # name, bench args
   for pass in "f FETCH_SIZE" "w WRITE_SIZE" "m SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
     set -- $pass; p=$1; shift
     rm -rf /tmp/pmc_${name}_$p
-    (cd /tmp && SIVO_LANES=1 timeout 240 rocprofv3 --pmc "$@" --output-format csv -d /tmp/pmc_${name}_$p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-orb --configs none $args > /dev/null 2>&1)
+    (cd /tmp && SIVO_LANES=1 timeout 240 rocprofv3 --pmc "$@" --output-format csv -d /tmp/pmc_${name}_$p -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-orb --configs none $args > /dev/null 2>&1)
   done
   python tools/pmc_summary.py $O/${TAG}_pmc_traffic_$name.json /tmp/pmc_${name}_f /tmp/pmc_${name}_w /tmp/pmc_${name}_m > /dev/null && python - <<PY
 import json
@@ -42,7 +42,7 @@ pmc t48 "--T 48"
 fi
 # the line reads its `traffic` from profiles/: the PMC passes of THIS build first
 [ -z "$LIGHT" ] && cp $O/${TAG}_pmc_traffic_*.json $R/profiles/ 2>/dev/null
-timeout 600 python bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.load(open("$O/${TAG}_bench_line.json")); r=d["roofline"]
@@ -52,7 +52,7 @@ PY
 stats() {   # name, bench args (quoted string), env...
   local name=$1 args=$2; shift 2
   rm -rf /tmp/prof_$name
-  (cd /tmp && env "$@" timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -o $name -- python $R/bench.py --serial --no-cpu-baseline --configs none $args > $O/${TAG}_bench_line_under_rocprof_$name.json 2>/dev/null)
+  (cd /tmp && env "$@" timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -o $name -- python $R/bench.py --full --serial --no-cpu-baseline --configs none $args > $O/${TAG}_bench_line_under_rocprof_$name.json 2>/dev/null)
   local f=$(find /tmp/prof_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/${TAG}_kernel_stats_${name}_incl_construction.csv
   local t=$(find /tmp/prof_$name -name "*kernel_trace.csv" | head -1)
