@@ -596,6 +596,48 @@ int sivo_pose_optimize(const double pose0[12], const double *points, int n_point
                        double cov[36], int *cov_ok, double *chi2, int *n_inliers, int *iterations,
                        int *trials);
 
+/* ---------------------------------------------------------------------------
+ * Optimizer::OptimizeSim3 from the point the graph is built (Optimizer.cc:1236-1449):
+ * one VertexSim3Expmap against EdgeSim3ProjectXYZ + EdgeInverseSim3ProjectXYZ per
+ * correspondence (points held fixed, g2o's numeric Jacobians), Huber kernels with
+ * delta = sqrtf(th2); optimize(5), a pair is an outlier if either chi2 > th2; fewer
+ * than 10 survivors -> *n_inliers = 0 and s12 unchanged (the flags of that test
+ * stay set); else optimize(10) if a pair was removed, optimize(5) if not, final
+ * test.  The whole schedule is one launch of one persistent workgroup per problem.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    double obs1[2], inv_sigma2_1; /* keypoint of KF1 (mvKeysSemantic[i]), mvInvLevelSigma2[octave] */
+    double obs2[2], inv_sigma2_2; /* keypoint of KF2 (mvKeysSemantic[i2]) */
+    double x1c[3], x2c[3];        /* map points in camera-1 / camera-2 coordinates (held fixed) */
+} SivoSim3Match;
+
+/* s12[8] in/out: qx qy qz qw tx ty tz s (g2o's Sim3 state).  k1, k2 = {fx, fy, cx, cy}.
+ * outlier[i] = 1: the pair the reference drops from vpMatches1.  chi2_12 / chi2_21: the
+ * chi2 of the two edges the last test read (a pair removed by the first test keeps the
+ * values of that test).  iterations / trials: LM iterations and trials of both
+ * optimize() calls.  Every output pointer other than s12 and n_inliers may be NULL. */
+int sivo_sim3_optimize(double s12[8], const double k1[4], const double k2[4], const SivoSim3Match *m, int n,
+                       float th2, int fix_scale, uint8_t *outlier, int *n_inliers, double *chi2_12,
+                       double *chi2_21, int *iterations, int *trials);
+
+/* One problem of sivo_sim3_optimize_batch: the arguments of sivo_sim3_optimize (s12 in/out),
+ * the three counts out. */
+typedef struct {
+    double s12[8], k1[4], k2[4];
+    const SivoSim3Match *matches;
+    int32_t n;
+    float th2;
+    int32_t fix_scale;
+    int32_t n_inliers;            /* out */
+    uint8_t *outlier;             /* n, may be NULL */
+    double *chi2_12, *chi2_21;    /* n each, may be NULL */
+    int32_t iterations, trials;   /* out */
+} SivoSim3Problem;
+
+/* n_problems independent problems (every loop candidate at once) in one launch, one
+ * workgroup each: every result is bit-identical to sivo_sim3_optimize on that problem. */
+int sivo_sim3_optimize_batch(SivoSim3Problem *problems, int n_problems);
+
 /* ===========================================================================
  * Entropy feature-selection gate (the Tracking form; sivo_check_semantics below is the LocalMapping form) — stands behind SIVO's sivo_helpers
  * (reference src/sivo_helpers/sivo_helpers.cpp:64-88 computeStereoJacobianPose,

@@ -60,6 +60,18 @@ class Edge(C.Structure):      # == SivoEdge (48 bytes)
                 ("obs", C.c_double * 3), ("inv_sigma2", C.c_double)]
 
 
+class Sim3Match(C.Structure):  # == SivoSim3Match (96 bytes)
+    _fields_ = [("obs1", C.c_double * 2), ("inv_sigma2_1", C.c_double), ("obs2", C.c_double * 2), ("inv_sigma2_2", C.c_double),
+                ("x1c", C.c_double * 3), ("x2c", C.c_double * 3)]
+
+
+class Sim3Problem(C.Structure):  # == SivoSim3Problem (one problem of sivo_sim3_optimize_batch)
+    _fields_ = [("s12", C.c_double * 8), ("k1", C.c_double * 4), ("k2", C.c_double * 4), ("matches", C.c_void_p),
+                ("n", C.c_int32), ("th2", C.c_float), ("fix_scale", C.c_int32), ("n_inliers", C.c_int32),
+                ("outlier", C.c_void_p), ("chi2_12", C.c_void_p), ("chi2_21", C.c_void_p),
+                ("iterations", C.c_int32), ("trials", C.c_int32)]
+
+
 _vp, _i, _i64, _u64, _sz, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_size_t, C.c_float, C.c_double
 _pi32 = C.POINTER(C.c_int32)
 
@@ -140,6 +152,8 @@ SIGNATURES = {
     "sivo_ba_optimize": [_vp, _vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _d, _d, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_local_ba": [_vp, _vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _vp, _vp, _i, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "sivo_pose_optimize": [_vp, _vp, _i, _vp, _i64, C.POINTER(_d), _vp, _vp, _vp, C.POINTER(_i), _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    "sivo_sim3_optimize": [_vp, C.POINTER(_d), C.POINTER(_d), _vp, _i, _f, _i, _vp, C.POINTER(_i), _vp, _vp, C.POINTER(_i), C.POINTER(_i)],
+    "sivo_sim3_optimize_batch": [_vp, _i],
     "sivo_ba_linearize_dev": [_vp, _vp, _vp, _i64, C.POINTER(_d), _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sivo_ba_linearize": [_vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }

@@ -16,9 +16,13 @@
 #define OPTIMIZER_ADAPTER_H
 
 #include <cmath>
+#include <cstring>
 #include <list>
 #include <map>
 #include <mutex>
+#include <stdexcept>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "Optimizer.h"
@@ -105,7 +109,126 @@ void set_covariance(T *obj, const double cov[36]) {
 #endif
 }
 
+// `R * X + t` of two CV_32F cv::Mats (3 x 3 by 3 x 1): gemm's small-matrix path, each dot product summed left to right in float,
+// then + t — the arithmetic ORBmatcher.h's matcher_detail::Pose::apply restates (pinned against the reference there)
+inline void cv_rx_plus_t(const cv::Mat &R, const cv::Mat &t, const cv::Mat &X, double out[3]) {
+    for (int r = 0; r < 3; ++r) {
+        float s = R.at<float>(r, 0) * X.at<float>(0, 0);
+        s = s + R.at<float>(r, 1) * X.at<float>(1, 0);
+        s = s + R.at<float>(r, 2) * X.at<float>(2, 0);
+        out[r] = (double)(s + t.at<float>(r, 0));
+    }
+}
+
+// The correspondences of Optimizer::OptimizeSim3 (Optimizer.cc:1294-1383): pair i of vpMatches1 enters when vpMatches1[i] and
+// pKF1's own map point i are both set and not bad and the match has an index in pKF2 (GetIndexInKeyFrame >= 0).  index[k] = i of
+// the k-th pair.  Points in camera coordinates with the float rounding of `R * Xw + t`; keypoints from mvKeysSemantic,
+// information mvInvLevelSigma2[octave].
+template <class KeyFrameT, class MapPointT>
+void gather_sim3(KeyFrameT *pKF1, KeyFrameT *pKF2, const std::vector<MapPointT *> &vpMatches1, std::vector<SivoSim3Match> &pairs,
+                 std::vector<size_t> &index) {
+    pairs.clear(); index.clear();
+    const cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation();
+    const cv::Mat R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+    const auto vpMapPoints1 = pKF1->GetMapPointMatches();
+    const int N = (int)vpMatches1.size();
+    for (int i = 0; i < N; ++i) {
+        if (!vpMatches1[i]) continue;
+        MapPointT *pMP1 = vpMapPoints1[i];
+        MapPointT *pMP2 = vpMatches1[i];
+        const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+        if (!pMP1 || pMP1->isBad() || pMP2->isBad() || i2 < 0) continue;
+        SivoSim3Match m{};
+        cv_rx_plus_t(R1w, t1w, pMP1->GetWorldPos(), m.x1c);
+        cv_rx_plus_t(R2w, t2w, pMP2->GetWorldPos(), m.x2c);
+        const cv::KeyPoint &kp1 = pKF1->mvKeysSemantic[i];
+        m.obs1[0] = kp1.pt.x; m.obs1[1] = kp1.pt.y;
+        m.inv_sigma2_1 = pKF1->mvInvLevelSigma2[kp1.octave];
+        const cv::KeyPoint &kp2 = pKF2->mvKeysSemantic[i2];
+        m.obs2[0] = kp2.pt.x; m.obs2[1] = kp2.pt.y;
+        m.inv_sigma2_2 = pKF2->mvInvLevelSigma2[kp2.octave];
+        pairs.push_back(m);
+        index.push_back((size_t)i);
+    }
+}
+
+// g2o::Sim3's rotation() is an Eigen quaternion; a stand-in may hand out a 3 x 3 matrix instead.  Read / write either as
+// (x, y, z, w); a matrix goes through Eigen's Quaternion(const Matrix3 &) construction (the trace branch) and back.
+template <class Q>
+auto sim3_rot_get(const Q &q, double o[4], int) -> decltype((void)q.w()) {
+    o[0] = q.x(); o[1] = q.y(); o[2] = q.z(); o[3] = q.w();
+}
+template <class M>
+void sim3_rot_get(const M &R, double o[4], long) {
+    const double t = R(0, 0) + R(1, 1) + R(2, 2);
+    if (t > 0.0) {
+        double s = std::sqrt(t + 1.0);
+        o[3] = 0.5 * s;
+        s = 0.5 / s;
+        o[0] = (R(2, 1) - R(1, 2)) * s; o[1] = (R(0, 2) - R(2, 0)) * s; o[2] = (R(1, 0) - R(0, 1)) * s;
+    } else {
+        int i = 0;
+        if (R(1, 1) > R(0, 0)) i = 1;
+        if (R(2, 2) > R(i, i)) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        double s = std::sqrt(R(i, i) - R(j, j) - R(k, k) + 1.0);
+        o[i] = 0.5 * s;
+        s = 0.5 / s;
+        o[3] = (R(k, j) - R(j, k)) * s; o[j] = (R(j, i) + R(i, j)) * s; o[k] = (R(k, i) + R(i, k)) * s;
+    }
+}
+template <class Q>
+auto sim3_rot_set(Q &q, const double v[4], int) -> decltype((void)(q.w() = 0.0)) {
+    q.x() = v[0]; q.y() = v[1]; q.z() = v[2]; q.w() = v[3];
+}
+template <class M>
+void sim3_rot_set(M &R, const double v[4], long) {
+    const double x = v[0], y = v[1], z = v[2], w = v[3];
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x,
+                 tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R(0, 0) = 1 - (tyy + tzz); R(0, 1) = txy - twz;       R(0, 2) = txz + twy;
+    R(1, 0) = txy + twz;       R(1, 1) = 1 - (txx + tzz); R(1, 2) = tyz - twx;
+    R(2, 0) = txz - twy;       R(2, 1) = tyz + twx;       R(2, 2) = 1 - (txx + tyy);
+}
+
 }  // namespace optimizer_detail
+
+// int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (Optimizer.cc:1236-1449) on the device: the pairs
+// gathered as the reference builds its graph, the whole optimisation (sivo_sim3_optimize), vpMatches1[i] nulled for every
+// outlier pair, g2oS12 written back through Sim3T's (rotation, translation, scale) constructor unless the reference returns
+// before that (fewer than 10 pairs survive the first test: 0, g2oS12 untouched).  Returns the inlier count.
+template <class KeyFrameT, class MapPointT, class Sim3T>
+int OptimizeSim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPointT *> &vpMatches1, Sim3T &g2oS12, const float th2,
+                 const bool bFixScale) {
+    using namespace optimizer_detail;
+    std::vector<SivoSim3Match> pairs;
+    std::vector<size_t> index;
+    gather_sim3(pKF1, pKF2, vpMatches1, pairs, index);
+    const cv::Mat &K1 = pKF1->mK, &K2 = pKF2->mK;
+    const double k1[4] = {K1.at<float>(0, 0), K1.at<float>(1, 1), K1.at<float>(0, 2), K1.at<float>(1, 2)};
+    const double k2[4] = {K2.at<float>(0, 0), K2.at<float>(1, 1), K2.at<float>(0, 2), K2.at<float>(1, 2)};
+    double s12[8], s_in[8];
+    sim3_rot_get(g2oS12.rotation(), s12, 0);
+    const auto t0 = g2oS12.translation();
+    for (int i = 0; i < 3; ++i) s12[4 + i] = t0[i];
+    s12[7] = g2oS12.scale();
+    std::memcpy(s_in, s12, sizeof s12);
+    std::vector<uint8_t> outlier(pairs.size());
+    int nIn = 0;
+    const int rc = sivo_sim3_optimize(s12, k1, k2, pairs.data(), (int)pairs.size(), th2, bFixScale ? 1 : 0, outlier.data(), &nIn,
+                                      nullptr, nullptr, nullptr, nullptr);
+    if (rc != SIVO_OK) throw std::runtime_error(std::string("sivo_sim3_optimize: ") + sivo_last_error());
+    for (size_t k = 0; k < pairs.size(); ++k)
+        if (outlier[k]) vpMatches1[index[k]] = nullptr;
+    if (nIn > 0 || std::memcmp(s12, s_in, sizeof s12) != 0) {
+        typename std::decay<decltype(g2oS12.rotation())>::type r = g2oS12.rotation();
+        typename std::decay<decltype(g2oS12.translation())>::type t = g2oS12.translation();
+        sim3_rot_set(r, s12, 0);
+        for (int i = 0; i < 3; ++i) t[i] = s12[4 + i];
+        g2oS12 = Sim3T(r, t, s12[7]);
+    }
+    return nIn;
+}
 
 // int Optimizer::PoseOptimization(Frame *pFrame)
 template <class FrameT>
@@ -334,7 +457,8 @@ void Optimizer::GlobalBundleAdjustment(MapT *pMap, int nIterations, bool *pbStop
     SIVO::GlobalBundleAdjustment(pMap, nIterations, pbStopFlag, nLoopKF, bRobust);
 }
 
-// Loop closing: Optimizer::OptimizeEssentialGraph / OptimizeSim3 (declared in Optimizer.h)
+// Loop closing: Optimizer::OptimizeEssentialGraph / OptimizeSim3 (declared in Optimizer.h).  With -DSIVO_HAVE_G2O both go to the
+// backend; otherwise OptimizeSim3 runs on the device under -DSIVO_SIM3_ON_DEVICE, and what is left is a compile-time error.
 #ifdef SIVO_HAVE_G2O
 template <class MapT, class KeyFrameT, class KFPoseMapT, class ConnectionsT>
 void Optimizer::OptimizeEssentialGraph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFPoseMapT &NonCorrectedSim3, const KFPoseMapT &CorrectedSim3,
@@ -351,12 +475,19 @@ void Optimizer::OptimizeEssentialGraph(MapT *, KeyFrameT *, KeyFrameT *, const K
     static_assert(sizeof(MapT) == 0, "Optimizer::OptimizeEssentialGraph (Sim3 pose graph, g2o) is outside this library: build with -DSIVO_HAVE_G2O and "
                                      "-DSIVO_G2O_BACKEND=<a class providing it, e.g. the reference's Optimizer.cc compiled under another name>");
 }
+#ifdef SIVO_SIM3_ON_DEVICE
+template <class KeyFrameT, class MapPointT, class Sim3T>
+int Optimizer::OptimizeSim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPointT *> &vpMatches1, Sim3T &g2oS12, const float th2, const bool bFixScale) {
+    return SIVO::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale);
+}
+#else
 template <class KeyFrameT, class MapPointT, class Sim3T>
 int Optimizer::OptimizeSim3(KeyFrameT *, KeyFrameT *, std::vector<MapPointT *> &, Sim3T &, const float, const bool) {
     static_assert(sizeof(KeyFrameT) == 0, "Optimizer::OptimizeSim3 (Sim3 alignment, g2o) is outside this library: build with -DSIVO_HAVE_G2O and "
-                                          "-DSIVO_G2O_BACKEND=<a class providing it>");
+                                          "-DSIVO_G2O_BACKEND=<a class providing it>, or with -DSIVO_SIM3_ON_DEVICE (this library's kernel)");
     return 0;
 }
+#endif
 #endif
 
 }  // namespace SIVO

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "solver_common.hpp"
 
 #pragma clang fp contract(off)
 
@@ -80,12 +81,6 @@ __device__ __forceinline__ void edge_eval(const double *P, const double *X, cons
             for (int j = 12; j < 18; ++j) jp[j] = 0.0;
         }
     }
-}
-
-__device__ __forceinline__ void huber(double c2, double delta, double &rho, double &w) {
-    const double dsqr = delta * delta;
-    if (c2 <= dsqr) { rho = c2; w = 1.0; }
-    else { const double s = sqrt(c2); rho = 2 * s * delta - dsqr; w = delta / s; }
 }
 
 // T <- exp([omega, upsilon]) * T   (g2o SE3Quat::exp, VertexSE3Expmap::oplusImpl)
@@ -163,42 +158,10 @@ __host__ __device__ inline bool inv6_spd(const double *H, double *out) {
     return true;
 }
 
-// x from lane (lane ^ M) for M = 1, 2, 8 on the VALU's data-parallel crossbar (no LDS traffic); 4, 16, 32 through ds_bpermute
-template <int M>
-__device__ __forceinline__ double lane_xor(double x) {
-    static_assert(M == 1 || M == 2 || M == 4 || M == 8 || M == 16 || M == 32, "");
-    if constexpr (M == 1 || M == 2 || M == 8) {
-        constexpr int ctrl = M == 1 ? 0xB1 /* quad_perm [1,0,3,2] */ : M == 2 ? 0x4E /* quad_perm [2,3,0,1] */ : 0x128 /* row_ror:8 */;
-        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), ctrl, 0xf, 0xf, false);
-        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), ctrl, 0xf, 0xf, false);
-        return __hiloint2double(hi, lo);
-    } else {
-        return __shfl_xor(x, M, 64);
-    }
-}
-
-// One step of the halving butterfly: a lane whose bit M is clear keeps v[0, N) and hands v[N, 2N) to its partner, the other way
-// round for a set bit; N values are left.
-template <int M, int N>
-__device__ __forceinline__ void halve_step(double *v, bool bit) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const double keep = bit ? v[N + j] : v[j], send = bit ? v[j] : v[N + j];
-        v[j] = keep + lane_xor<M>(send);
-    }
-}
-
 // The same sum as block_sum for K > ~8 values: the wave step is a butterfly that HALVES the values a lane carries at every
 // exchange (reduce-scatter: P/2 + P/4 + ... + 1 exchanges for P = K rounded up to a power of two, instead of 6 K), after which
 // lane l holds the wave's total of ONE slot; the rest of the butterfly adds that slot over the lanes that share it.  Waves in
 // index order after that.  A fixed order: the result does not depend on timing.  v has P entries, entries >= K are zero.
-template <int P>
-__device__ __forceinline__ int halving_slot(int lane) {       // the slot whose total lane `lane` ends up with
-    int s = 0;
-#pragma unroll
-    for (int b = 0; (1 << b) < P; ++b) s |= ((lane >> b) & 1) << ((P == 64 ? 5 : P == 32 ? 4 : 3) - b);
-    return s;
-}
 template <int K, int P, int NT>
 __device__ __forceinline__ void block_sum_h(const double (&v)[K], double *s_red /* [NT/64][P] */, double *s_out /* [K] */) {
     static_assert((P == 16 || P == 32 || P == 64) && K <= P && 2 * K > P, "P = K rounded up to a power of two");

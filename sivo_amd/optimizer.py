@@ -6,11 +6,14 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Edge, check, lib
+from ._lib import Edge, Sim3Match, Sim3Problem, check, lib
 
 EDGE_DTYPE = np.dtype([("pose", np.int32), ("point", np.int32), ("stereo", np.int32), ("pad_", np.int32),
                        ("obs", np.float64, 3), ("inv_sigma2", np.float64)])
 assert EDGE_DTYPE.itemsize == C.sizeof(Edge) == 48
+SIM3_MATCH_DTYPE = np.dtype([("obs1", np.float64, 2), ("inv_sigma2_1", np.float64), ("obs2", np.float64, 2),
+                             ("inv_sigma2_2", np.float64), ("x1c", np.float64, 3), ("x2c", np.float64, 3)])
+assert SIM3_MATCH_DTYPE.itemsize == C.sizeof(Sim3Match) == 96
 TH_HUBER_MONO = math.sqrt(5.991)     # Optimizer.cc:647
 TH_HUBER_STEREO = math.sqrt(7.815)   # Optimizer.cc:648
 
@@ -90,3 +93,47 @@ def pose_optimize(pose0, points, edges, intr):
                                    _vp(pose), _vp(cov), C.byref(ok), _vp(chi2), C.byref(inl), C.byref(n), C.byref(tr)))
     return {"pose": pose, "outlier": outlier, "cov": cov, "cov_ok": bool(ok.value), "chi2": chi2, "inliers": inl.value,
             "iterations": n.value, "trials": tr.value}
+
+
+def _sim3_args(s12, k1, k2, matches):
+    s12 = np.array(s12, np.float64).reshape(8).copy()
+    k1 = (C.c_double * 4)(*[float(v) for v in k1]); k2 = (C.c_double * 4)(*[float(v) for v in k2])
+    return s12, k1, k2, np.ascontiguousarray(matches, SIM3_MATCH_DTYPE)
+
+
+def sim3_optimize(s12, k1, k2, matches, th2=10.0, fix_scale=True):
+    """Optimizer::OptimizeSim3 (reference Optimizer.cc:1236-1449) from the built graph on: s12 = qx qy qz qw tx ty tz s (g2o::Sim3),
+    k1 / k2 = fx fy cx cy, matches = SIM3_MATCH_DTYPE records.  Returns the optimised s12 (the input when fewer than 10 pairs survive),
+    the outlier flags (the vpMatches1 entries the reference nulls), the inlier count (its return value), the chi2 values the last
+    test read and the iteration / trial counts of both optimize() calls."""
+    s12, k1, k2, m = _sim3_args(s12, k1, k2, matches)
+    n = m.shape[0]
+    outlier = np.zeros(n, np.uint8); c12 = np.zeros(n); c21 = np.zeros(n)
+    inl = C.c_int(0); it = C.c_int(0); tr = C.c_int(0)
+    check(lib().sivo_sim3_optimize(_vp(s12), k1, k2, _vp(m), n, float(th2), int(bool(fix_scale)), _vp(outlier), C.byref(inl),
+                                   _vp(c12), _vp(c21), C.byref(it), C.byref(tr)))
+    return {"s12": s12, "outlier": outlier, "inliers": inl.value, "chi2_12": c12, "chi2_21": c21, "iterations": it.value,
+            "trials": tr.value}
+
+
+def sim3_optimize_batch(problems):
+    """k independent OptimizeSim3 problems in one launch (one workgroup each): `problems` is a list of dicts with the arguments of
+    sim3_optimize (s12, k1, k2, matches, optional th2 / fix_scale).  Returns a list of the dicts sim3_optimize returns; each is
+    bit-identical to the single call on the same problem."""
+    P = (Sim3Problem * max(len(problems), 1))()
+    keep, out = [], []
+    for i, p in enumerate(problems):
+        s12, k1, k2, m = _sim3_args(p["s12"], p["k1"], p["k2"], p["matches"])
+        n = m.shape[0]
+        r = {"s12": s12, "outlier": np.zeros(n, np.uint8), "chi2_12": np.zeros(n), "chi2_21": np.zeros(n)}
+        P[i].s12[:] = list(s12); P[i].k1[:] = list(k1); P[i].k2[:] = list(k2)
+        P[i].matches = m.ctypes.data if n else None; P[i].n = n
+        P[i].th2 = float(p.get("th2", 10.0)); P[i].fix_scale = int(bool(p.get("fix_scale", True)))
+        P[i].outlier = r["outlier"].ctypes.data if n else None
+        P[i].chi2_12 = r["chi2_12"].ctypes.data if n else None; P[i].chi2_21 = r["chi2_21"].ctypes.data if n else None
+        keep.append(m); out.append(r)
+    check(lib().sivo_sim3_optimize_batch(C.cast(P, C.c_void_p), len(problems)))
+    for i, r in enumerate(out):
+        r["s12"] = np.array(P[i].s12[:], np.float64)
+        r["inliers"] = P[i].n_inliers; r["iterations"] = P[i].iterations; r["trials"] = P[i].trials
+    return out
