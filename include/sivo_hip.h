@@ -638,6 +638,47 @@ typedef struct {
  * workgroup each: every result is bit-identical to sivo_sim3_optimize on that problem. */
 int sivo_sim3_optimize_batch(SivoSim3Problem *problems, int n_problems);
 
+/* ---------------------------------------------------------------------------
+ * Optimizer::OptimizeEssentialGraph from the point the graph is built
+ * (Optimizer.cc:928-1180: the graph of :964-1175, then optimize(20)): one
+ * VertexSim3Expmap per keyframe, EdgeSim3 edges with information I7 and no robust
+ * kernel, error = log(Sji * Si * Sj^-1) (g2o's Sim3::log), BaseBinaryEdge's numeric
+ * Jacobians (central differences, delta = 1e-9, through oplus), Levenberg-Marquardt
+ * with lambda_0 = 1e-16 (setUserLambdaInit) over the sparse 7n x 7n system.
+ * The host orders the variables and factors the pattern symbolically once per call;
+ * the device assembles H, factors H + lambda I by sparse block Cholesky, solves,
+ * updates and takes every LM decision.  Results are bit-identical run to run.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    int32_t i, j;                 /* vertex 0 / vertex 1 of the EdgeSim3 (indices into siw) */
+    double meas[8];               /* Sji: qx qy qz qw tx ty tz s */
+} SivoSim3Edge;
+
+/* siw[8 n] in/out: Siw of vertex k (qx qy qz qw tx ty tz s); fixed[n]: 1 = setFixed(true).
+ * A vertex without edges, or fixed, keeps its estimate.  No edge, or no vertex both
+ * free and on an edge: no iteration (g2o's optimize() returns at once).  fix_scale:
+ * VertexSim3Expmap::_fix_scale (update[6] = 0).  chi2[2] (may be NULL): sum of e'e over
+ * the edges at the input and at the returned estimate.  iterations_done / trials may
+ * be NULL.  Index out of range, i == j, a non-positive scale or a NULL array with a
+ * non-zero count -> SIVO_ERR_INVALID_ARGUMENT before any device is touched. */
+int sivo_essential_graph_optimize(double *siw, const uint8_t *fixed, int n, const SivoSim3Edge *e, int ne,
+                                  int fix_scale, int iterations, double *chi2, int *iterations_done,
+                                  int *trials);
+
+/* The host half of sivo_essential_graph_optimize on its own (no device): the ordering
+ * and symbolic factorisation it would use.  out[6]: variables (free vertices on an
+ * edge), block columns of L that are not diagonal, nnz(L) in scalars (lower triangle),
+ * flops of one numeric factorisation, levels of the elimination tree, pattern blocks
+ * of H below the diagonal. */
+int sivo_essential_graph_analyze(const uint8_t *fixed, int n, const SivoSim3Edge *e, int ne, int64_t out[6]);
+
+/* The map-point correction of OptimizeEssentialGraph (Optimizer.cc:1205-1233):
+ * out[k] = (float) correctedSwr.map(Srw.map((double) xyz[k])) with Srw = siw_before[r],
+ * correctedSwr = siw_after[r]^-1, r = ref[k]; ref[k] = -1: out[k] = xyz[k].  xyz, out:
+ * 3 np floats (may alias). */
+int sivo_sim3_correct_points(const float *xyz, const int32_t *ref, int np, const double *siw_before,
+                             const double *siw_after, int n, float *out);
+
 /* ===========================================================================
  * Entropy feature-selection gate (the Tracking form; sivo_check_semantics below is the LocalMapping form) — stands behind SIVO's sivo_helpers
  * (reference src/sivo_helpers/sivo_helpers.cpp:64-88 computeStereoJacobianPose,

@@ -72,6 +72,10 @@ class Sim3Problem(C.Structure):  # == SivoSim3Problem (one problem of sivo_sim3_
                 ("iterations", C.c_int32), ("trials", C.c_int32)]
 
 
+class Sim3Edge(C.Structure):   # == SivoSim3Edge (72 bytes): one EdgeSim3 of sivo_essential_graph_optimize
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("meas", C.c_double * 8)]
+
+
 _vp, _i, _i64, _u64, _sz, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_size_t, C.c_float, C.c_double
 _pi32 = C.POINTER(C.c_int32)
 
@@ -154,6 +158,9 @@ SIGNATURES = {
     "sivo_pose_optimize": [_vp, _vp, _i, _vp, _i64, C.POINTER(_d), _vp, _vp, _vp, C.POINTER(_i), _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "sivo_sim3_optimize": [_vp, C.POINTER(_d), C.POINTER(_d), _vp, _i, _f, _i, _vp, C.POINTER(_i), _vp, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_sim3_optimize_batch": [_vp, _i],
+    "sivo_essential_graph_optimize": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
+    "sivo_essential_graph_analyze": [_vp, _i, _vp, _i, _vp],
+    "sivo_sim3_correct_points": [_vp, _vp, _i, _vp, _vp, _i, _vp],
     "sivo_ba_linearize_dev": [_vp, _vp, _vp, _i64, C.POINTER(_d), _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sivo_ba_linearize": [_vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }

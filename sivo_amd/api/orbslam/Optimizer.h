@@ -83,13 +83,14 @@ class Optimizer {
 
     // ---- loop closing (reference include/orbslam/Optimizer.h:64-79; called at LoopClosing.cc:333 `Optimizer::OptimizeSim3(mpCurrentKF,
     // pKF, vpMapPointMatches, gScm, 10, mbFixScale)` and :582 `Optimizer::OptimizeEssentialGraph(mpMap, mpMatchedKF, mpCurrentKF,
-    // NonCorrectedSim3, CorrectedSim3, LoopConnections, mbFixScale)`).  Sim3 pose-graph optimisation: sequential sparse algebra over a
-    // pointer graph, a handful of calls per loop closure — SLAM back end, outside the per-frame path this library accelerates
-    // (out of scope).  The members exist so that LoopClosing.cc compiles against this class unchanged: with
-    // -DSIVO_HAVE_G2O they forward to SIVO_G2O_BACKEND (a class with these two static members: the reference's own Optimizer.cc
-    // compiled under another name is one — tests/cpp/pin_optimizer.cpp links exactly that); without it, -DSIVO_SIM3_ON_DEVICE
-    // routes OptimizeSim3 to SIVO::OptimizeSim3 (OptimizerAdapter.h: the whole alignment in one launch, sivo_sim3_optimize), and
-    // instantiating what is left without a backend is a compile-time error that says so.
+    // NonCorrectedSim3, CorrectedSim3, LoopConnections, mbFixScale)`).  Sim3 alignment and Sim3 pose-graph optimisation, a handful of
+    // calls per loop closure, outside the per-frame path.  The members exist so that LoopClosing.cc compiles against this class
+    // unchanged: with -DSIVO_HAVE_G2O they forward to SIVO_G2O_BACKEND (a class with these two static members: the reference's own
+    // Optimizer.cc compiled under another name is one — tests/cpp/pin_optimizer.cpp links exactly that); without it,
+    // -DSIVO_SIM3_ON_DEVICE routes OptimizeSim3 to SIVO::OptimizeSim3 (OptimizerAdapter.h: the whole alignment in one launch,
+    // sivo_sim3_optimize) and -DSIVO_ESSENTIAL_GRAPH_ON_DEVICE routes OptimizeEssentialGraph to SIVO::OptimizeEssentialGraph (the
+    // graph walk, sivo_essential_graph_optimize's sparse LM on the device, the pose and point write-back); instantiating a member
+    // without its macro or a backend is a compile-time error that says so.
     template <class MapT, class KeyFrameT, class KFPoseMapT, class ConnectionsT>
     static void OptimizeEssentialGraph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFPoseMapT &NonCorrectedSim3,
                                        const KFPoseMapT &CorrectedSim3, const ConnectionsT &LoopConnections, const bool &bFixScale);

@@ -20,6 +20,7 @@
 #include <list>
 #include <map>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -191,7 +192,226 @@ void sim3_rot_set(M &R, const double v[4], long) {
     R(2, 0) = txz - twy;       R(2, 1) = tyz + twx;       R(2, 2) = 1 - (txx + tyy);
 }
 
+// g2o::Sim3 on the host, for the measurements of OptimizeEssentialGraph: (x y z w, t, s) with the product and inverse in Eigen's
+// operation order (the device's sim3_common.hpp restates the same)
+struct HostSim3 { double q[4], t[3], s; };
+inline void host_quat_rotate(const double q[4], const double v[3], double o[3]) {
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    double u0 = y * v[2] - z * v[1], u1 = z * v[0] - x * v[2], u2 = x * v[1] - y * v[0];
+    u0 = u0 + u0; u1 = u1 + u1; u2 = u2 + u2;
+    o[0] = v[0] + w * u0 + (y * u2 - z * u1);
+    o[1] = v[1] + w * u1 + (z * u0 - x * u2);
+    o[2] = v[2] + w * u2 + (x * u1 - y * u0);
+}
+inline HostSim3 host_sim3_mul(const HostSim3 &a, const HostSim3 &b) {
+    HostSim3 o;
+    const double ax = a.q[0], ay = a.q[1], az = a.q[2], aw = a.q[3], bx = b.q[0], by = b.q[1], bz = b.q[2], bw = b.q[3];
+    o.q[0] = aw * bx + ax * bw + ay * bz - az * by;
+    o.q[1] = aw * by + ay * bw + az * bx - ax * bz;
+    o.q[2] = aw * bz + az * bw + ax * by - ay * bx;
+    o.q[3] = aw * bw - ax * bx - ay * by - az * bz;
+    double r[3];
+    host_quat_rotate(a.q, b.t, r);
+    for (int i = 0; i < 3; ++i) o.t[i] = a.s * r[i] + a.t[i];
+    o.s = a.s * b.s;
+    return o;
+}
+inline HostSim3 host_sim3_inv(const HostSim3 &a) {
+    HostSim3 o;
+    o.q[0] = -a.q[0]; o.q[1] = -a.q[1]; o.q[2] = -a.q[2]; o.q[3] = a.q[3];
+    const double f = -1. / a.s;
+    const double ft[3] = {f * a.t[0], f * a.t[1], f * a.t[2]};
+    host_quat_rotate(o.q, ft, o.t);
+    o.s = 1. / a.s;
+    return o;
+}
+// g2o::Sim3(Rcw, tcw, 1.0) from a keyframe pose (Optimizer.cc:984-989): Quaterniond(R) of the float rotation, not normalised
+template <class KeyFrameT>
+HostSim3 host_sim3_of_pose(KeyFrameT *pKF) {
+    const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation();
+    double M[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) M[r][c] = R.at<float>(r, c);
+    struct { const double (*m)[3]; double operator()(int r, int c) const { return m[r][c]; } } Rm{M};
+    HostSim3 S;
+    sim3_rot_get(Rm, S.q, 0);
+    for (int r = 0; r < 3; ++r) S.t[r] = t.at<float>(r, 0);
+    S.s = 1.0;
+    return S;
+}
+template <class Sim3T>
+HostSim3 host_sim3_of(const Sim3T &g) {
+    HostSim3 S;
+    sim3_rot_get(g.rotation(), S.q, 0);
+    const auto t = g.translation();
+    for (int i = 0; i < 3; ++i) S.t[i] = t[i];
+    S.s = g.scale();
+    return S;
+}
+inline void host_sim3_store(const HostSim3 &S, double o[8]) {
+    for (int i = 0; i < 4; ++i) o[i] = S.q[i];
+    for (int i = 0; i < 3; ++i) o[4 + i] = S.t[i];
+    o[7] = S.s;
+}
+inline HostSim3 host_sim3_load(const double o[8]) {
+    HostSim3 S;
+    for (int i = 0; i < 4; ++i) S.q[i] = o[i];
+    for (int i = 0; i < 3; ++i) S.t[i] = o[4 + i];
+    S.s = o[7];
+    return S;
+}
+
+// The graph of Optimizer::OptimizeEssentialGraph (Optimizer.cc:964-1175), in the reference's order.  siw[8 (maxKFid + 1)]: vScw —
+// the vertex estimates (CorrectedSim3 if present, else Sim3(Rcw, tcw, 1)), identity where there is no vertex; fixed: pLoopKF;
+// vertex: which ids have one.  Edges: first the LoopConnections (weight >= 100, or the (pCurKF, pLoopKF) pair; measurements from
+// vScw), then per keyframe of GetAllKeyFrames() the spanning-tree edge, the loop edges to smaller ids and the covisibility edges
+// (GetCovisiblesByWeight(100), smaller id, not parent / child / loop edge / bad / already a LoopConnections pair), their Swi / Sjw
+// from NonCorrectedSim3 where present.  A bad keyframe in the list is skipped in the normal-edge walk, and an edge to a keyframe
+// without a vertex is left out: the reference would hand g2o a null vertex there.
+template <class MapT, class KeyFrameT, class KFPoseMapT, class ConnectionsT>
+void gather_essential_graph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFPoseMapT &NonCorrectedSim3,
+                            const KFPoseMapT &CorrectedSim3, const ConnectionsT &LoopConnections, std::vector<double> &siw,
+                            std::vector<uint8_t> &fixed, std::vector<uint8_t> &vertex, std::vector<SivoSim3Edge> &edges) {
+    const auto vpKFs = pMap->GetAllKeyFrames();
+    const size_t n = (size_t)pMap->GetMaxKFid() + 1;
+    const double I[8] = {0, 0, 0, 1, 0, 0, 0, 1};
+    siw.assign(8 * n, 0.0);
+    for (size_t v = 0; v < n; ++v) std::memcpy(&siw[8 * v], I, sizeof I);
+    fixed.assign(n, 0);
+    vertex.assign(n, 0);
+    edges.clear();
+    for (KeyFrameT *pKF : vpKFs) {                                   // vertices (:964-1006)
+        if (pKF->isBad()) continue;
+        const size_t id = (size_t)pKF->mnId;
+        if (id >= n) continue;
+        const auto it = CorrectedSim3.find(pKF);
+        const HostSim3 S = it != CorrectedSim3.end() ? host_sim3_of(it->second) : host_sim3_of_pose(pKF);
+        host_sim3_store(S, &siw[8 * id]);
+        vertex[id] = 1;
+        if (pKF == pLoopKF) fixed[id] = 1;
+    }
+    auto has_vertex = [&](size_t id) { return id < n && vertex[id]; };
+    auto add = [&](size_t i, size_t j, const HostSim3 &Sji) {
+        if (!has_vertex(i) || !has_vertex(j)) return;
+        SivoSim3Edge e{};
+        e.i = (int32_t)i; e.j = (int32_t)j;
+        host_sim3_store(Sji, e.meas);
+        edges.push_back(e);
+    };
+    const int minFeat = 100;
+    std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+    for (const auto &conn : LoopConnections) {                      // loop edges (:1011-1049)
+        KeyFrameT *pKF = conn.first;
+        const unsigned long nIDi = pKF->mnId;
+        const HostSim3 Swi = host_sim3_inv(nIDi < n ? host_sim3_load(&siw[8 * nIDi]) : host_sim3_load(I));
+        for (KeyFrameT *pKFj : conn.second) {
+            const unsigned long nIDj = pKFj->mnId;
+            if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(pKFj) < minFeat) continue;
+            const HostSim3 Sjw = nIDj < n ? host_sim3_load(&siw[8 * nIDj]) : host_sim3_load(I);
+            add(nIDi, nIDj, host_sim3_mul(Sjw, Swi));
+            sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+        }
+    }
+    auto s_w = [&](KeyFrameT *pK) {                                   // NonCorrectedSim3 if present, else vScw
+        const auto it = NonCorrectedSim3.find(pK);
+        if (it != NonCorrectedSim3.end()) return host_sim3_of(it->second);
+        const size_t id = (size_t)pK->mnId;
+        return id < n ? host_sim3_load(&siw[8 * id]) : host_sim3_load(I);
+    };
+    for (KeyFrameT *pKF : vpKFs) {                                   // normal edges (:1052-1175)
+        if (pKF->isBad()) continue;
+        const unsigned long nIDi = pKF->mnId;
+        const HostSim3 Swi = host_sim3_inv(s_w(pKF));
+        KeyFrameT *pParentKF = pKF->GetParent();
+        if (pParentKF) add(nIDi, pParentKF->mnId, host_sim3_mul(s_w(pParentKF), Swi));
+        const auto sLoopEdges = pKF->GetLoopEdges();
+        for (KeyFrameT *pLKF : sLoopEdges)
+            if (pLKF->mnId < pKF->mnId) add(nIDi, pLKF->mnId, host_sim3_mul(s_w(pLKF), Swi));
+        const auto vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+        for (KeyFrameT *pKFn : vpConnectedKFs) {
+            if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+                if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                    if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+                    add(nIDi, pKFn->mnId, host_sim3_mul(s_w(pKFn), Swi));
+                }
+            }
+        }
+    }
+}
+
+// SetPose of the write-back (Optimizer.cc:1184-1203): Sim3 [sR t] -> SE3 [R t/s]: R = toRotationMatrix, eigt *= 1. / s, both to float
+inline cv::Mat cv_pose_from_sim3(const double S[8]) {
+    double R[9];
+    {
+        const double x = S[0], y = S[1], z = S[2], w = S[3];
+        const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x,
+                     tyy = ty * y, tyz = tz * y, tzz = tz * z;
+        const double M[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+        for (int i = 0; i < 9; ++i) R[i] = M[i];
+    }
+    const double f = 1. / S[7];
+    cv::Mat T = cv::Mat::eye(4, 4, CV_32F);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) T.at<float>(r, c) = (float)R[3 * r + c];
+        T.at<float>(r, 3) = (float)(S[4 + r] * f);
+    }
+    return T;
+}
+
 }  // namespace optimizer_detail
+
+// void Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale)
+// (Optimizer.cc:928-1233) on the device: the graph gathered as the reference builds it, optimize(20) (sivo_essential_graph_optimize),
+// then under pMap->mMutexMapUpdate the keyframe poses (SetPose([R | t/s])) and the map points (correctedSwr.map(Srw.map(P)),
+// sivo_sim3_correct_points; SetWorldPos + UpdateNormalAndDepth).  Keyframes that are bad or have no vertex are skipped in the
+// write-back (the reference would dereference a null vertex there); a point whose reference keyframe has no vertex keeps its position
+// (the reference maps it through two identities).
+template <class MapT, class KeyFrameT, class KFPoseMapT, class ConnectionsT>
+void OptimizeEssentialGraph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFPoseMapT &NonCorrectedSim3, const KFPoseMapT &CorrectedSim3,
+                            const ConnectionsT &LoopConnections, const bool &bFixScale) {
+    using namespace optimizer_detail;
+    std::vector<double> siw;
+    std::vector<uint8_t> fixed, vertex;
+    std::vector<SivoSim3Edge> edges;
+    gather_essential_graph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, siw, fixed, vertex, edges);
+    const std::vector<double> vScw = siw;
+    const int n = (int)fixed.size();
+    int rc = sivo_essential_graph_optimize(siw.data(), fixed.data(), n, edges.data(), (int)edges.size(), bFixScale ? 1 : 0, 20, nullptr,
+                                           nullptr, nullptr);
+    if (rc != SIVO_OK) throw std::runtime_error(std::string("sivo_essential_graph_optimize: ") + sivo_last_error());
+    const auto vpKFs = pMap->GetAllKeyFrames();
+    const auto vpMPs = pMap->GetAllMapPoints();
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    for (KeyFrameT *pKFi : vpKFs) {
+        const size_t id = (size_t)pKFi->mnId;
+        if (pKFi->isBad() || id >= (size_t)n || !vertex[id]) continue;      // (no vertex: the reference dereferences null here)
+        pKFi->SetPose(cv_pose_from_sim3(&siw[8 * id]));
+    }
+    std::vector<decltype(vpMPs.size())> which;
+    std::vector<float> xyz;
+    std::vector<int32_t> ref;
+    for (size_t i = 0; i < vpMPs.size(); ++i) {
+        auto *pMP = vpMPs[i];
+        if (pMP->isBad()) continue;
+        long nIDr;
+        if (pMP->mnCorrectedByKF == pCurKF->mnId) nIDr = (long)pMP->mnCorrectedReference;
+        else nIDr = (long)pMP->GetReferenceKeyFrame()->mnId;
+        const cv::Mat P = pMP->GetWorldPos();
+        for (int r = 0; r < 3; ++r) xyz.push_back(P.at<float>(r, 0));
+        ref.push_back(nIDr >= 0 && nIDr < n && vertex[(size_t)nIDr] ? (int32_t)nIDr : -1);
+        which.push_back(i);
+    }
+    std::vector<float> out(xyz.size());
+    rc = sivo_sim3_correct_points(xyz.data(), ref.data(), (int)ref.size(), vScw.data(), siw.data(), n, out.data());
+    if (rc != SIVO_OK) throw std::runtime_error(std::string("sivo_sim3_correct_points: ") + sivo_last_error());
+    for (size_t k = 0; k < which.size(); ++k) {
+        auto *pMP = vpMPs[which[k]];
+        cv::Mat X(3, 1, CV_32F);
+        for (int r = 0; r < 3; ++r) X.at<float>(r, 0) = out[3 * k + r];
+        pMP->SetWorldPos(X);
+        pMP->UpdateNormalAndDepth();
+    }
+}
 
 // int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (Optimizer.cc:1236-1449) on the device: the pairs
 // gathered as the reference builds its graph, the whole optimisation (sivo_sim3_optimize), vpMatches1[i] nulled for every
@@ -458,7 +678,8 @@ void Optimizer::GlobalBundleAdjustment(MapT *pMap, int nIterations, bool *pbStop
 }
 
 // Loop closing: Optimizer::OptimizeEssentialGraph / OptimizeSim3 (declared in Optimizer.h).  With -DSIVO_HAVE_G2O both go to the
-// backend; otherwise OptimizeSim3 runs on the device under -DSIVO_SIM3_ON_DEVICE, and what is left is a compile-time error.
+// backend; otherwise OptimizeSim3 runs on the device under -DSIVO_SIM3_ON_DEVICE and OptimizeEssentialGraph under
+// -DSIVO_ESSENTIAL_GRAPH_ON_DEVICE, and what is left is a compile-time error.
 #ifdef SIVO_HAVE_G2O
 template <class MapT, class KeyFrameT, class KFPoseMapT, class ConnectionsT>
 void Optimizer::OptimizeEssentialGraph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFPoseMapT &NonCorrectedSim3, const KFPoseMapT &CorrectedSim3,
@@ -470,11 +691,20 @@ int Optimizer::OptimizeSim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPoi
     return SIVO_G2O_BACKEND::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale);
 }
 #else
+#ifdef SIVO_ESSENTIAL_GRAPH_ON_DEVICE
+template <class MapT, class KeyFrameT, class KFPoseMapT, class ConnectionsT>
+void Optimizer::OptimizeEssentialGraph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFPoseMapT &NonCorrectedSim3, const KFPoseMapT &CorrectedSim3,
+                                       const ConnectionsT &LoopConnections, const bool &bFixScale) {
+    SIVO::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale);
+}
+#else
 template <class MapT, class KeyFrameT, class KFPoseMapT, class ConnectionsT>
 void Optimizer::OptimizeEssentialGraph(MapT *, KeyFrameT *, KeyFrameT *, const KFPoseMapT &, const KFPoseMapT &, const ConnectionsT &, const bool &) {
     static_assert(sizeof(MapT) == 0, "Optimizer::OptimizeEssentialGraph (Sim3 pose graph, g2o) is outside this library: build with -DSIVO_HAVE_G2O and "
-                                     "-DSIVO_G2O_BACKEND=<a class providing it, e.g. the reference's Optimizer.cc compiled under another name>");
+                                     "-DSIVO_G2O_BACKEND=<a class providing it, e.g. the reference's Optimizer.cc compiled under another name>, "
+                                     "or with -DSIVO_ESSENTIAL_GRAPH_ON_DEVICE (this library's kernels)");
 }
+#endif
 #ifdef SIVO_SIM3_ON_DEVICE
 template <class KeyFrameT, class MapPointT, class Sim3T>
 int Optimizer::OptimizeSim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPointT *> &vpMatches1, Sim3T &g2oS12, const float th2, const bool bFixScale) {

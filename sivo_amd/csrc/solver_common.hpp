@@ -1,5 +1,5 @@
-// solver_common.hpp — device pieces shared by the persistent-workgroup solvers (ba_solve.hip, sim3.hip): the Huber kernel of g2o's
-// RobustKernelHuber and the fixed-order lane reductions.
+// solver_common.hpp — device pieces shared by the persistent-workgroup solvers (ba_solve.hip, sim3.hip, essential_graph.hip): the Huber
+// kernel of g2o's RobustKernelHuber, the fixed-order lane reductions and a small dense Cholesky.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,5 +42,46 @@ __device__ __forceinline__ int halving_slot(int lane) {       // the slot whose 
 #pragma unroll
     for (int b = 0; (1 << b) < P; ++b) s |= ((lane >> b) & 1) << ((P == 64 ? 5 : P == 32 ? 4 : 3) - b);
     return s;
+}
+
+// lower Cholesky factor of the N x N matrix A (row-major, lower triangle read), the reciprocals of its diagonal in rd
+template <int N>
+__device__ __forceinline__ bool chol_recip(double (&A)[N * N], double (&rd)[N]) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        double d = A[j * N + j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= A[j * N + k] * A[j * N + k];
+        ok = ok && (d > 0.0);
+        d = sqrt(d);
+        A[j * N + j] = d;
+        rd[j] = 1.0 / d;
+#pragma unroll
+        for (int i = j + 1; i < N; ++i) {
+            double s = A[i * N + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= A[i * N + k] * A[j * N + k];
+            A[i * N + j] = s * rd[j];
+        }
+    }
+    return ok;
+}
+template <int N>
+__device__ __forceinline__ void chol_recip_solve(const double (&L)[N * N], const double (&rd)[N], double (&x)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double s = x[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= L[i * N + k] * x[k];
+        x[i] = s * rd[i];
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+        double s = x[i];
+#pragma unroll
+        for (int k = i + 1; k < N; ++k) s -= L[k * N + i] * x[k];
+        x[i] = s * rd[i];
+    }
 }
 }  // namespace sivo

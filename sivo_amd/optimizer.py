@@ -6,7 +6,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Edge, Sim3Match, Sim3Problem, check, lib
+from ._lib import Edge, Sim3Edge, Sim3Match, Sim3Problem, check, lib
 
 EDGE_DTYPE = np.dtype([("pose", np.int32), ("point", np.int32), ("stereo", np.int32), ("pad_", np.int32),
                        ("obs", np.float64, 3), ("inv_sigma2", np.float64)])
@@ -14,6 +14,8 @@ assert EDGE_DTYPE.itemsize == C.sizeof(Edge) == 48
 SIM3_MATCH_DTYPE = np.dtype([("obs1", np.float64, 2), ("inv_sigma2_1", np.float64), ("obs2", np.float64, 2),
                              ("inv_sigma2_2", np.float64), ("x1c", np.float64, 3), ("x2c", np.float64, 3)])
 assert SIM3_MATCH_DTYPE.itemsize == C.sizeof(Sim3Match) == 96
+SIM3_EDGE_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("meas", np.float64, 8)])
+assert SIM3_EDGE_DTYPE.itemsize == C.sizeof(Sim3Edge) == 72
 TH_HUBER_MONO = math.sqrt(5.991)     # Optimizer.cc:647
 TH_HUBER_STEREO = math.sqrt(7.815)   # Optimizer.cc:648
 
@@ -136,4 +138,47 @@ def sim3_optimize_batch(problems):
     for i, r in enumerate(out):
         r["s12"] = np.array(P[i].s12[:], np.float64)
         r["inliers"] = P[i].n_inliers; r["iterations"] = P[i].iterations; r["trials"] = P[i].trials
+    return out
+
+
+def _graph_args(siw, fixed, edges):
+    siw = np.array(siw, np.float64).reshape(-1, 8).copy()
+    n = siw.shape[0]
+    fixed = np.ascontiguousarray(np.asarray(fixed, bool).reshape(n), np.uint8)
+    return siw, fixed, np.ascontiguousarray(edges, SIM3_EDGE_DTYPE)
+
+
+def essential_graph_optimize(siw, fixed, edges, fix_scale=True, iterations=20):
+    """Optimizer::OptimizeEssentialGraph (reference Optimizer.cc:928-1180) from the built graph on: siw (n, 8) = qx qy qz qw tx ty tz s
+    of every vertex (g2o::Sim3), fixed (n,) bool, edges = SIM3_EDGE_DTYPE records (i = vertex 0, j = vertex 1, meas = Sji).  Returns
+    the optimised siw (a new array), the chi2 (sum of e'e) at the start and at the end, and the LM iteration / trial counts."""
+    siw, fixed, e = _graph_args(siw, fixed, edges)
+    chi2 = np.zeros(2)
+    it = C.c_int(0); tr = C.c_int(0)
+    check(lib().sivo_essential_graph_optimize(_vp(siw), _vp(fixed), siw.shape[0], _vp(e), e.shape[0], int(bool(fix_scale)),
+                                              int(iterations), _vp(chi2), C.byref(it), C.byref(tr)))
+    return {"siw": siw, "chi2_start": float(chi2[0]), "chi2": float(chi2[1]), "iterations": it.value, "trials": tr.value}
+
+
+def essential_graph_analyze(fixed, edges):
+    """The ordering and symbolic factorisation essential_graph_optimize uses, host only: variables, off-diagonal blocks of L,
+    nnz(L) (scalars, lower triangle), flops of one numeric factorisation, elimination-tree levels, off-diagonal blocks of H."""
+    fixed = np.ascontiguousarray(np.asarray(fixed, bool), np.uint8)
+    e = np.ascontiguousarray(edges, SIM3_EDGE_DTYPE)
+    out = np.zeros(6, np.int64)
+    check(lib().sivo_essential_graph_analyze(_vp(fixed), fixed.shape[0], _vp(e), e.shape[0], _vp(out)))
+    return dict(zip(("variables", "l_blocks", "nnz_l", "flops", "levels", "h_blocks"), (int(v) for v in out)))
+
+
+def sim3_correct_points(xyz, ref, siw_before, siw_after):
+    """The map-point correction of OptimizeEssentialGraph (Optimizer.cc:1205-1233): for point k with r = ref[k] >= 0,
+    (float) siw_after[r]^-1 . map(siw_before[r] . map((double) xyz[k])); ref[k] = -1 leaves the point as it is."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    ref = np.ascontiguousarray(ref, np.int32).reshape(-1)
+    before = np.ascontiguousarray(siw_before, np.float64).reshape(-1, 8)
+    after = np.ascontiguousarray(siw_after, np.float64).reshape(-1, 8)
+    if ref.shape[0] != xyz.shape[0] or before.shape != after.shape:
+        raise ValueError("xyz / ref or siw_before / siw_after differ in length")
+    out = np.empty_like(xyz)
+    check(lib().sivo_sim3_correct_points(_vp(xyz), _vp(ref), xyz.shape[0], _vp(before), _vp(after), before.shape[0], _vp(out)))
     return out
