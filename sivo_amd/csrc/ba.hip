@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "common.hpp"
+#include "solver_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -132,22 +133,17 @@ extern "C" int sivo_ba_linearize(const double *poses, int n_poses, const double 
         for (int64_t e = 0; e < n_edges; ++e)
             if (edges[e].pose < 0 || edges[e].pose >= n_poses || edges[e].point < 0 || edges[e].point >= n_points)
                 throw std::invalid_argument("edge refers to a pose/point outside the arrays");
-        if (sivo_device_count() < 1) return fail(SIVO_ERR_RUNTIME, "no HIP device: libsivo_hip has no CPU fallback");
-        struct Buf { void *p = nullptr; ~Buf() { (void)hipFree(p); } };
-        auto up = [](Buf &b, const void *src, size_t bytes) {
-            SIVO_HIP(hipMalloc(&b.p, bytes ? bytes : 1));
-            if (src) SIVO_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-        };
-        Buf dP, dX, dE, dErr, dJx, dJp, dC, dR, dW, dOk;
-        up(dP, poses, (size_t)n_poses * 12 * 8); up(dX, points, (size_t)n_points * 3 * 8);
-        up(dE, edges, (size_t)n_edges * sizeof(SivoEdge));
-        up(dErr, nullptr, n_edges * 3 * 8); up(dJx, nullptr, n_edges * 9 * 8); up(dJp, nullptr, n_edges * 18 * 8);
-        up(dC, nullptr, n_edges * 8); up(dR, nullptr, n_edges * 8); up(dW, nullptr, n_edges * 8); up(dOk, nullptr, n_edges);
+        require_device();
+        CallBuf dP, dX, dE, dErr, dJx, dJp, dC, dR, dW, dOk;
+        dP.up(poses, (size_t)n_poses * 12 * 8); dX.up(points, (size_t)n_points * 3 * 8);
+        dE.up(edges, (size_t)n_edges * sizeof(SivoEdge));
+        dErr.up(nullptr, n_edges * 3 * 8); dJx.up(nullptr, n_edges * 9 * 8); dJp.up(nullptr, n_edges * 18 * 8);
+        dC.up(nullptr, n_edges * 8); dR.up(nullptr, n_edges * 8); dW.up(nullptr, n_edges * 8); dOk.up(nullptr, n_edges);
         int rc = sivo_ba_linearize_dev((const double *)dP.p, (const double *)dX.p, (const SivoEdge *)dE.p, n_edges, intr,
                                        delta_mono, delta_stereo, (double *)dErr.p, (double *)dJx.p, (double *)dJp.p,
                                        (double *)dC.p, (double *)dR.p, (double *)dW.p, (uint8_t *)dOk.p, nullptr);
         if (rc) return rc;
-        auto down = [](void *dst, const Buf &b, size_t bytes) { if (dst) SIVO_HIP(hipMemcpy(dst, b.p, bytes, hipMemcpyDeviceToHost)); };
+        auto down = [](void *dst, const CallBuf &b, size_t bytes) { if (dst) SIVO_HIP(hipMemcpy(dst, b.p, bytes, hipMemcpyDeviceToHost)); };
         down(err, dErr, n_edges * 3 * 8); down(jx, dJx, n_edges * 9 * 8); down(jp, dJp, n_edges * 18 * 8);
         down(chi2, dC, n_edges * 8); down(rho, dR, n_edges * 8); down(w, dW, n_edges * 8); down(depth_ok, dOk, n_edges);
         return SIVO_OK;

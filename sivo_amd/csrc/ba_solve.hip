@@ -28,11 +28,11 @@
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
-#include <mutex>
 #include <vector>
 
 #include "common.hpp"
 #include "solver_common.hpp"
+#include "solver_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -472,22 +472,14 @@ __global__ __launch_bounds__(PO_THREADS) void pose_optimize_kernel(PoseOptArgs a
                     chi += r;
                 }
                 const double chi_sum = red.sum1(chi);
-                const double temp = ok ? chi_sum : DBL_MAX;
-                const double rho = (current - temp) / (scale + 1e-3);
-                if (rho > 0 && isfinite(temp)) {
-                    const double t = 2 * rho - 1;
-                    double alpha = 1. - t * t * t;
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2; current = temp;
-                } else {
-                    lambda *= ni; ni *= 2;
+                const LmTrial tr = lm_trial(current, ok ? chi_sum : DBL_MAX, scale, lambda, ni);
+                if (!tr.accepted) {
 #pragma unroll
                     for (int i = 0; i < 12; ++i) P[i] = Bk[i];
                 }
                 ++qmax; ++trials;
-                cont = (rho < 0 && qmax < 10);
-                term = (qmax == 10 || rho == 0);
+                cont = (tr.rho < 0 && qmax < 10);
+                term = (qmax == 10 || tr.rho == 0);
             } while (cont);
             ++iters;
             if (term) break;
@@ -603,24 +595,13 @@ __device__ __forceinline__ void ba_lm_decide(const BaDev &d, double r0, double r
     BaLm &m = *d.lm;
     if (!m.have_current) { m.current = d.scal[6]; m.have_current = 1; }
     const bool ok = d.scal[3] != 0.0;
-    const double temp = ok ? r0 : DBL_MAX;
-    const double scale = ok ? d.scal[1] + (landmarks ? r4 : 0.0) : 0.0;
-    const double rho = (m.current - temp) / (scale + 1e-3);
-    if (rho > 0 && isfinite(temp)) {
-        const double t = 2 * rho - 1;
-        double alpha = 1. - t * t * t;                  // (as pose_optimize_kernel)
-        alpha = fmin(alpha, 2. / 3.);
-        m.lambda *= fmax(1. / 3., alpha);
-        m.ni = 2; m.current = temp;
-        m.cur ^= 1;                                     // (the trial kernel left errors, Jacobians and W of the new estimate in its set)
-    } else {
-        m.lambda *= m.ni; m.ni *= 2;
-    }
-    m.rho = rho;
+    const LmTrial tr = lm_trial(m.current, ok ? r0 : DBL_MAX, ok ? d.scal[1] + (landmarks ? r4 : 0.0) : 0.0, m.lambda, m.ni);
+    if (tr.accepted) m.cur ^= 1;                        // (the trial kernel left errors, Jacobians and W of the new estimate in its set)
+    m.rho = tr.rho;
     ++m.qmax; ++m.trials;
     const bool stop = d.abort && __atomic_load_n(d.abort, __ATOMIC_RELAXED) != 0;
-    if (rho < 0 && m.qmax < 10 && !stop) { m.need_lin = 0; return; }          // another trial of the same iteration
-    const bool brk = m.qmax == 10 || rho == 0;
+    if (tr.rho < 0 && m.qmax < 10 && !stop) { m.need_lin = 0; return; }          // another trial of the same iteration
+    const bool brk = m.qmax == 10 || tr.rho == 0;
     ++m.it;
     if (brk || stop || m.it >= m.it_limit) { m.done = 1; return; }
     m.need_lin = 1; m.qmax = 0; m.have_current = 0;
@@ -1286,24 +1267,9 @@ struct BaArena {
     }
 };
 static thread_local BaArena t_arena;
-// Per-thread, grow-only pinned staging buffer for a solver's one upload (a pinned allocation costs ~0.2 ms: never per call).  Its content
-// is in flight until the call's first blocking read (the LM state after the first batch of steps), which every call makes before it returns.
-struct BaStage {
-    char *p = nullptr;
-    size_t cap = 0;
-    ~BaStage() { if (p) (void)hipHostFree(p); }
-    char *reserve(size_t bytes) {
-        if (bytes > cap) {
-            if (p) SIVO_HIP(hipHostFree(p));
-            p = nullptr; cap = 0;
-            const size_t want = std::max(bytes * 2, (size_t)8 << 20);
-            SIVO_HIP(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-            cap = want;
-        }
-        return p;
-    }
-};
-static thread_local BaStage t_stage;
+// Per-thread pinned staging buffer for a solver's one upload.  Its content is in flight until the call's first blocking read (the LM
+// state after the first batch of steps), which every call makes before it returns.
+static thread_local PinnedBuf t_stage(8 << 20);
 
 struct Buf {
     void *p = nullptr;
@@ -1314,17 +1280,16 @@ struct Buf {
 };
 
 // The LDS-resident Cholesky needs up to 127 KB of dynamic LDS: the opt-in is per device and per process, so it is made once
-// per device under a lock and its result is kept; a device that refuses it uses the global-memory kernel.
+// per device and its result is kept; a device that refuses it uses the global-memory kernel.
 static bool dense_solve_lds_ok() {
-    static std::mutex mu;
-    static int state[64] = {0};                 // per device: 0 unknown, 1 granted, -1 refused
+    static int once[64];
+    static bool refused[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    std::lock_guard<std::mutex> lock(mu);
-    if (state[dev] == 0)
-        state[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(ba_dense_solve_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         127 * 127 * 8) == hipSuccess ? 1 : -1;
-    return state[dev] == 1;
+    if (FirstUse first(once); first)
+        refused[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(ba_dense_solve_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           127 * 127 * 8) != hipSuccess;
+    return !refused[dev];
 }
 
 // What the stop flag of a solver call needs, once per calling thread (a pinned allocation costs 0.2 ms: not per call): a pinned word the
@@ -1386,32 +1351,22 @@ class BaSolver {
         // round 5 were 24 blocking calls of ~15 us each — a tenth of the LocalBundleAdjustment call.  The host arrays are packed into the
         // calling thread's pinned staging buffer and go over in one asynchronous copy; everything that starts at zero is one region.
         {
-            struct Seg { Buf *b; const void *src; size_t bytes; };
-            const Seg up[] = {{&slot_, slot.data(), slot.size() * 4}, {&pt_off_, pt_off.data(), pt_off.size() * 8}, {&pt_edges_, pt_edges.data(), pt_edges.size() * 4},
-                              {&ps_off_, ps_off.data(), ps_off.size() * 8}, {&ps_edges_, ps_edges.data(), ps_edges.size() * 4}, {&table_, table.data(), table.size() * 4},
-                              {&edges_, edges, (size_t)nE * sizeof(SivoEdge)}, {&poses_[0], poses, (size_t)nP * 96}, {&poses_[1], poses, (size_t)nP * 96},
-                              {&points_[0], points, (size_t)nX * 24}, {&points_[1], points, (size_t)nX * 24}};
-            auto pad = [](size_t n) { return (std::max<size_t>(n, 8) + 255) / 256 * 256; };
-            size_t total = 0;
-            for (const Seg &g : up) total += pad(g.bytes);
-            char *dev = (char *)t_arena.take(total), *host = t_stage.reserve(total);
-            size_t off = 0;
-            for (const Seg &g : up) {
-                if (g.bytes) std::memcpy(host + off, g.src, g.bytes);
-                g.b->p = dev + off;
-                off += pad(g.bytes);
-            }
-            SIVO_HIP(hipMemcpyAsync(dev, host, total, hipMemcpyHostToDevice, 0));
-            struct Z { Buf *b; size_t bytes; };
-            const Z zs[] = {{&level_, (size_t)nE}, {&err_[0], (size_t)nE * 24}, {&err_[1], (size_t)nE * 24}, {&rchi_[0], (size_t)nE * 8}, {&rchi_[1], (size_t)nE * 8},
-                            {&sc_pt_, (size_t)nX * 8}, {&Hpp_, (size_t)nF_ * 288}, {&bp_, (size_t)nF_ * 48}, {&xs_, (size_t)nF_ * 48}, {&scal_, 8 * 8},
-                            {&partial_, (size_t)cdiv64(std::max<int64_t>(nE, 1), BA_T) * 8}, {&counter_, 8}, {&lm_, sizeof(BaLm)}};
-            size_t ztotal = 0;
-            for (const Z &z : zs) ztotal += pad(z.bytes);
-            char *zdev = (char *)t_arena.take(ztotal);
-            off = 0;
-            for (const Z &z : zs) { z.b->p = zdev + off; off += pad(z.bytes); }
-            SIVO_HIP(hipMemsetAsync(zdev, 0, ztotal, 0));
+            Layout L;
+            L.copy(slot_.p, slot.data(), slot.size() * 4); L.copy(pt_off_.p, pt_off.data(), pt_off.size() * 8);
+            L.copy(pt_edges_.p, pt_edges.data(), pt_edges.size() * 4); L.copy(ps_off_.p, ps_off.data(), ps_off.size() * 8);
+            L.copy(ps_edges_.p, ps_edges.data(), ps_edges.size() * 4); L.copy(table_.p, table.data(), table.size() * 4);
+            L.copy(edges_.p, edges, (size_t)nE * sizeof(SivoEdge));
+            for (int k = 0; k < 2; ++k) { L.copy(poses_[k].p, poses, (size_t)nP * 96); L.copy(points_[k].p, points, (size_t)nX * 24); }
+            L.zero(level_.p, (size_t)nE);
+            for (int k = 0; k < 2; ++k) { L.zero(err_[k].p, (size_t)nE * 24); L.zero(rchi_[k].p, (size_t)nE * 8); }
+            L.zero(sc_pt_.p, (size_t)nX * 8); L.zero(Hpp_.p, (size_t)nF_ * 288); L.zero(bp_.p, (size_t)nF_ * 48); L.zero(xs_.p, (size_t)nF_ * 48);
+            L.zero(scal_.p, 8 * 8); L.zero(partial_.p, (size_t)cdiv64(std::max<int64_t>(nE, 1), BA_T) * 8); L.zero(counter_.p, 8);
+            L.zero(lm_.p, sizeof(BaLm));
+            // optimize() uploads its initial state from the slot behind the staged problem, which is still in flight then
+            char *host = t_stage.reserve(L.staged() + sizeof(LmSlot));
+            slot_stage_ = (LmSlot *)(host + L.staged());
+            L.place((char *)t_arena.take(L.bytes()), host);
+            L.send(0);
         }
         robust_.alloc((size_t)nE);
         SIVO_HIP(hipMemsetAsync(robust_.p, 1, (size_t)std::max<int64_t>(nE, 1), 0));
@@ -1461,8 +1416,10 @@ class BaSolver {
         }
         BaLm lm{};
         lm.ni = 2; lm.cur = cur_; lm.need_lin = 1; lm.first = 1; lm.it_limit = iterations; lm.last_set = last_set_;
-        SIVO_HIP(hipMemcpyAsync(d_.lm, &lm, sizeof lm, hipMemcpyHostToDevice, 0));          // (pageable source: the copy is staged before the call returns)
-        if (!nF_) { const double one = 1.0; SIVO_HIP(hipMemcpyAsync(d_.scal + 3, &one, 8, hipMemcpyHostToDevice, 0)); }      // nothing to solve: "ok"
+        // (from pinned memory: the copies read it after this call has returned; the previous optimize() ended with a blocking read)
+        slot_stage_->lm = lm;
+        SIVO_HIP(hipMemcpyAsync(d_.lm, &slot_stage_->lm, sizeof lm, hipMemcpyHostToDevice, 0));
+        if (!nF_) { slot_stage_->ok = 1.0; SIVO_HIP(hipMemcpyAsync(d_.scal + 3, &slot_stage_->ok, 8, hipMemcpyHostToDevice, 0)); }      // nothing to solve: "ok"
         const bool lds_solve = 6 * nF_ <= 126 && dense_solve_lds_ok();
         auto step = [&](bool first_of_call) {
             // linearise at the current estimate: errors, Jacobians, W (first step of a call only: afterwards the accepted trial left them);
@@ -1544,6 +1501,7 @@ class BaSolver {
     Buf err_[2], Jp_[2], Jx_[2], wo_[2], rchi_[2], W_[2], Hll_, bl_, xl_, sc_pt_, Hpp_, bp_, S_, xs_, scal_, partial_, counter_, lm_;
     int last_set_ = 0;
     int *abort_host_ = nullptr;            // (the calling thread's pinned word, BaStopCtx)
+    struct LmSlot { BaLm lm; double ok; } *slot_stage_ = nullptr;      // (in t_stage)
     std::vector<double> hpp_last_;
     std::vector<int32_t> slot_host_;
     BaDev d_{};
@@ -1553,10 +1511,6 @@ class BaSolver {
 
 using namespace sivo;
 
-static void need_gpu() {
-    if (sivo_device_count() < 1) throw std::runtime_error("no HIP device: libsivo_hip has no CPU fallback");
-}
-
 extern "C" int sivo_ba_optimize(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
                                 const SivoEdge *edges, int64_t n_edges, const double intr[5], double delta_mono,
                                 double delta_stereo, const uint8_t *level, const uint8_t *robust, int iterations,
@@ -1565,7 +1519,7 @@ extern "C" int sivo_ba_optimize(double *poses, const uint8_t *pose_fixed, int n_
     return guarded([&] {
         if (!poses || !intr || (n_edges && !edges) || (n_points && !points)) throw std::invalid_argument("null argument");
         if (iterations < 0) throw std::invalid_argument("negative iteration count");
-        need_gpu();
+        require_device();
         t_arena.reset();
         BaSolver s(poses, pose_fixed, n_poses, points, n_points, false, edges, n_edges, intr, delta_mono, delta_stereo);
         s.set_flags(level, robust);
@@ -1584,7 +1538,7 @@ extern "C" int sivo_local_ba(double *poses, const uint8_t *pose_fixed, int n_pos
                              uint8_t *outlier, int cov_pose, double *cov, int *cov_ok, int *iterations, int *trials) {
     return guarded([&] {
         if (!poses || !intr || (n_edges && !edges) || (n_points && !points)) throw std::invalid_argument("null argument");
-        need_gpu();
+        require_device();
         if (iterations) *iterations = 0;
         if (trials) *trials = 0;
         if (cov_ok) *cov_ok = 0;
@@ -1611,56 +1565,6 @@ extern "C" int sivo_local_ba(double *poses, const uint8_t *pose_fixed, int n_pos
     });
 }
 
-// Per-thread state of sivo_pose_optimize (PoseOptimization runs once or more per frame on the tracking thread): pinned host
-// buffers the kernel reads its input from and writes its results to, and a stream of its own (the null stream is also
-// PyTorch's default stream: a per-frame solve must not queue behind whatever the host application runs there).  Grow-only,
-// released when the thread exits; nothing is allocated in a call once the buffers fit.
-struct PoseCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    void *h_in = nullptr, *h_out = nullptr;
-    size_t cap_in = 0, cap_out = 0;
-    void release() {
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-        if (stream) (void)hipStreamDestroy(stream);
-        h_in = h_out = nullptr; stream = nullptr; cap_in = cap_out = 0;
-    }
-    ~PoseCtx() { release(); }
-    void reserve(size_t in_bytes, size_t out_bytes) {
-        if (in_bytes > cap_in) {
-            if (h_in) SIVO_HIP(hipHostFree(h_in));
-            h_in = nullptr; cap_in = 0;
-            const size_t cap = std::max(in_bytes * 2, (size_t)256 << 10);
-            SIVO_HIP(hipHostMalloc(&h_in, cap, hipHostMallocDefault));
-            cap_in = cap;
-        }
-        if (out_bytes > cap_out) {
-            if (h_out) SIVO_HIP(hipHostFree(h_out));
-            h_out = nullptr; cap_out = 0;
-            const size_t cap = std::max(out_bytes * 2, (size_t)64 << 10);
-            SIVO_HIP(hipHostMalloc(&h_out, cap, hipHostMallocDefault));
-            cap_out = cap;
-        }
-    }
-};
-static PoseCtx &pose_ctx() {
-    static thread_local PoseCtx c;
-    int dev = 0;
-    SIVO_HIP(hipGetDevice(&dev));
-    if (c.device != dev) {
-        c.release();
-        int lo = 0, hi = 0;
-        SIVO_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        SIVO_HIP(hipStreamCreateWithPriority(&c.stream, hipStreamNonBlocking, hi));
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lock(mu);
-        SIVO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pose_optimize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS_BYTES));
-        c.device = dev;
-    }
-    return c;
-}
-
 extern "C" int sivo_pose_optimize(const double pose0[12], const double *points, int n_points, const SivoEdge *edges,
                                   int64_t n_edges, const double intr[5], uint8_t *outlier, double pose_out[12],
                                   double cov[36], int *cov_ok, double *chi2, int *n_inliers, int *iterations,
@@ -1679,11 +1583,16 @@ extern "C" int sivo_pose_optimize(const double pose0[12], const double *points, 
             if (n_edges) std::memset(outlier, 0, (size_t)n_edges);
             return SIVO_OK;
         }
-        need_gpu();
-        PoseCtx &c = pose_ctx();
+        require_device();
+        // PoseOptimization runs once or more per frame on the tracking thread: pinned buffers the kernel reads its input from and
+        // writes its results to, kept per thread
+        static thread_local SolverCtx c(true, 256 << 10, 64 << 10, 0);
+        c.bind();
+        static int once[64];
+        if (FirstUse first(once); first)
+            SIVO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pose_optimize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS_BYTES));
         const size_t in_doubles = 12 + 8 * (size_t)n_edges, out_doubles = 52 + (chi2 ? (size_t)n_edges : 0);
-        c.reserve(in_doubles * 8, out_doubles * 8 + (size_t)n_edges);
-        double *in = (double *)c.h_in;
+        double *in = (double *)c.in.reserve(in_doubles * 8);
         std::memcpy(in, pose0, 96);
         for (int64_t e = 0; e < n_edges; ++e) {
             double *q = in + 12 + 8 * e;
@@ -1696,7 +1605,7 @@ extern "C" int sivo_pose_optimize(const double pose0[12], const double *points, 
         a.K = Intr{intr[0], intr[1], intr[2], intr[3], intr[4]};
         a.delta_mono = (double)std::sqrt(5.991f); a.delta_stereo = (double)std::sqrt(7.815f);   // :307-308
         a.want_chi2 = chi2 != nullptr;
-        double *h_out = (double *)c.h_out;
+        double *h_out = (double *)c.out.reserve(out_doubles * 8 + (size_t)n_edges);
         uint8_t *h_flag = (uint8_t *)(h_out + out_doubles);
         if (n_edges <= PO_CAP) {
             // the kernel reads the staged edges once (into LDS) and writes a few hundred bytes: both straight through the pinned

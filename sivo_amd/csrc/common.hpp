@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <stdexcept>
 #include <string>
 
 #include "../../include/sivo_hip.h"
@@ -39,6 +40,11 @@ int guarded(F &&body) {
     } catch (const std::exception &x) {
         return fail(SIVO_ERR_RUNTIME, "%s", x.what());
     }
+}
+
+// The product has no CPU fallback: a compute entry point called without a HIP device fails (inside guarded(): SIVO_ERR_RUNTIME).
+inline void require_device() {
+    if (sivo_device_count() < 1) throw std::runtime_error("no HIP device: libsivo_hip has no CPU fallback");
 }
 
 struct DeviceGuard {

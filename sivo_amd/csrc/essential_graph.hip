@@ -32,6 +32,7 @@
 #include "common.hpp"
 #include "sim3_common.hpp"
 #include "solver_common.hpp"
+#include "solver_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -475,23 +476,13 @@ __global__ __launch_bounds__(EG_T) void eg_chi2_kernel(EgDev d, int mode) {
     *d.counter = 0u;
     if (mode) { m.current = chi; m.chi_init = chi; return; }
     // OptimizationAlgorithmLevenberg::solve, one trial
-    const double temp = m.ok ? chi : DBL_MAX;
-    const double rho = (m.current - temp) / (m.scale + 1e-3);
-    if (rho > 0 && isfinite(temp)) {
-        const double t = 2 * rho - 1;
-        double alpha = 1. - t * t * t;
-        alpha = fmin(alpha, 2. / 3.);
-        m.lambda *= fmax(1. / 3., alpha);
-        m.ni = 2; m.current = temp;
-        m.cur ^= 1;
-    } else {
-        m.lambda *= m.ni; m.ni *= 2;
-    }
-    m.rho = rho;
+    const LmTrial tr = lm_trial(m.current, m.ok ? chi : DBL_MAX, m.scale, m.lambda, m.ni);
+    if (tr.accepted) m.cur ^= 1;
+    m.rho = tr.rho;
     ++m.qmax; ++m.trials;
-    if (rho < 0 && m.qmax < 10) { m.need_lin = 0; return; }          // another trial of the same iteration
+    if (tr.rho < 0 && m.qmax < 10) { m.need_lin = 0; return; }          // another trial of the same iteration
     ++m.it;
-    if (m.qmax == 10 || rho == 0 || m.it >= m.it_limit) { m.done = 1; return; }
+    if (m.qmax == 10 || tr.rho == 0 || m.it >= m.it_limit) { m.done = 1; return; }
     m.need_lin = 1; m.qmax = 0;
 }
 
@@ -679,60 +670,9 @@ static void eg_plan(const uint8_t *fixed, int n, const SivoSim3Edge *e, int ne, 
 // ------------------------------------------------------------------------------------------------
 // host side: the device context (one per process, guarded by a mutex: loop closing runs on one thread) and the call
 // ------------------------------------------------------------------------------------------------
-struct EgCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    void *h_in = nullptr, *d_buf = nullptr, *h_out = nullptr;
-    size_t cap_in = 0, cap_buf = 0, cap_out = 0;
-    void release() {
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-        if (d_buf) (void)hipFree(d_buf);
-        if (stream) (void)hipStreamDestroy(stream);
-        h_in = h_out = d_buf = nullptr; stream = nullptr; cap_in = cap_buf = cap_out = 0;
-    }
-    ~EgCtx() { release(); }
-    void reserve(size_t in_bytes, size_t buf_bytes, size_t out_bytes) {
-        if (in_bytes > cap_in) {
-            if (h_in) SIVO_HIP(hipHostFree(h_in));
-            h_in = nullptr; cap_in = 0;
-            const size_t cap = std::max(in_bytes + in_bytes / 2, (size_t)256 << 10);
-            SIVO_HIP(hipHostMalloc(&h_in, cap, hipHostMallocDefault));
-            cap_in = cap;
-        }
-        if (out_bytes > cap_out) {
-            if (h_out) SIVO_HIP(hipHostFree(h_out));
-            h_out = nullptr; cap_out = 0;
-            const size_t cap = std::max(out_bytes + out_bytes / 2, (size_t)64 << 10);
-            SIVO_HIP(hipHostMalloc(&h_out, cap, hipHostMallocDefault));
-            cap_out = cap;
-        }
-        if (buf_bytes > cap_buf) {
-            if (d_buf) SIVO_HIP(hipFree(d_buf));
-            d_buf = nullptr; cap_buf = 0;
-            const size_t cap = std::max(buf_bytes + buf_bytes / 2, (size_t)1 << 20);
-            SIVO_HIP(hipMalloc(&d_buf, cap));
-            cap_buf = cap;
-        }
-    }
-};
+// (never destroyed: no HIP call from a static destructor at exit)
 static std::mutex eg_mu;
-static EgCtx &eg_ctx() {                       // (eg_mu held; never destroyed: no HIP call from a static destructor at exit)
-    static EgCtx &c = *new EgCtx;
-    int dev = 0;
-    SIVO_HIP(hipGetDevice(&dev));
-    if (c.device != dev) {
-        c.release();
-        SIVO_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-        c.device = dev;
-    }
-    return c;
-}
-
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// a region of the staging layout: host source (may be null: device-only), bytes
-struct EgRegion { const void *src; size_t bytes; size_t off; };
+static SolverCtx &eg_ctx = *new SolverCtx(false, 256 << 10, 64 << 10, 1 << 20);
 
 static int eg_run(double *siw, const uint8_t *fixed, int n, const SivoSim3Edge *e, int ne, int fix_scale, int iterations, double *chi2,
                   int *iterations_done, int *trials) {
@@ -745,7 +685,7 @@ static int eg_run(double *siw, const uint8_t *fixed, int n, const SivoSim3Edge *
     if (iterations_done) *iterations_done = 0;
     if (trials) *trials = 0;
     if (n == 0) return SIVO_OK;
-    if (sivo_device_count() < 1) throw std::runtime_error("no HIP device: libsivo_hip has no CPU fallback");
+    require_device();
     if (ne == 0) return SIVO_OK;                                  // (no edge: no active vertex, chi2 = 0, nothing to do)
     EgPlan P;
     eg_plan(fixed, n, e, ne, P);
@@ -756,74 +696,38 @@ static int eg_run(double *siw, const uint8_t *fixed, int n, const SivoSim3Edge *
         std::memcpy(meas.data() + 8 * (size_t)k, e[k].meas, 64);
     }
     const int na = P.na, nL = P.nL;
-    // staging: the inputs (one copy up), the device-only work arrays (one memset), the state
-    EgRegion R[] = {
-        {siw, 64 * (size_t)n},                                   //  0 est0
-        {nullptr, 64 * (size_t)n},                               //  1 est1
-        {P.vpos.data(), 4 * P.vpos.size()},                      //  2
-        {eij.data(), 4 * eij.size()},                            //  3
-        {meas.data(), 8 * meas.size()},                          //  4
-        {P.own_blk.data(), 4 * P.own_blk.size()},                //  5
-        {P.own_ptr.data(), 4 * P.own_ptr.size()},                //  6
-        {P.own_con.data(), 4 * P.own_con.size()},                //  7
-        {P.lvl_ptr.data(), 4 * P.lvl_ptr.size()},                //  8
-        {P.lvl_col.data(), 4 * P.lvl_col.size()},                //  9
-        {P.off_ptr.data(), 4 * P.off_ptr.size()},                // 10
-        {P.off_blk.data(), 4 * P.off_blk.size()},                // 11
-        {P.blk_col.data(), 4 * P.blk_col.size()},                // 12
-        {P.pair_ptr.data(), 4 * P.pair_ptr.size()},              // 13
-        {P.pairs.data(), 4 * P.pairs.size()},                    // 14
-        {P.row_ptr.data(), 4 * P.row_ptr.size()},                // 15
-        {P.row_lst.data(), 4 * P.row_lst.size()},                // 16
-        {P.col_ptr.data(), 4 * P.col_ptr.size()},                // 17
-        {P.col_lst.data(), 4 * P.col_lst.size()},                // 18
-        {nullptr, sizeof(EgLm)},                                 // 19 lm (uploaded: the initial state)
-        // ---- device only, zeroed once
-        {nullptr, 4},                                            // 20 counter
-        {nullptr, 49 * 8 * (size_t)nL},                          // 21 H (the fill blocks stay zero)
-        {nullptr, 224 * 8 * (size_t)na},                         // 22 pert
-        {nullptr, EG_NERR * 7 * 8 * (size_t)ne},                 // 23 errs
-        {nullptr, 8 * (size_t)ne},                               // 24 chi
-        {nullptr, 7 * 8 * (size_t)na},                           // 25 b
-        {nullptr, 49 * 8 * (size_t)nL},                          // 26 L
-        {nullptr, 7 * 8 * (size_t)na},                           // 27 rinv
-        {nullptr, 7 * 8 * (size_t)na},                           // 28 x
-    };
-    constexpr int NR = sizeof(R) / sizeof(R[0]), N_UP = 20;
-    size_t off = 0;
-    for (int k = 0; k < NR; ++k) { R[k].off = off; off += al256(std::max<size_t>(R[k].bytes, 8)); }
-    const size_t up_bytes = R[N_UP].off, total = off;
     EgLm lm0{};
     lm0.lambda = 1e-16;                       // setUserLambdaInit(1e-16): computeLambdaInit returns it at iteration 0
     lm0.ni = 2; lm0.need_lin = 1; lm0.it_limit = iterations;
-    R[19].src = &lm0;
-    std::lock_guard<std::mutex> lock(eg_mu);
-    EgCtx &c = eg_ctx();
-    c.reserve(up_bytes, total, sizeof(EgLm) + 64 * (size_t)n + 64);
-    unsigned char *hin = (unsigned char *)c.h_in, *db = (unsigned char *)c.d_buf;
-    for (int k = 0; k < N_UP; ++k)
-        if (R[k].src && R[k].bytes) std::memcpy(hin + R[k].off, R[k].src, R[k].bytes);
+    // staging: the inputs and the initial state (one copy up), the device-only work arrays (one memset)
     EgDev d;
-    d.est0 = (double *)(db + R[0].off); d.est1 = (double *)(db + R[1].off);
-    d.vpos = (const int *)(db + R[2].off); d.eij = (const int *)(db + R[3].off); d.meas = (const double *)(db + R[4].off);
-    d.own_blk = (const int *)(db + R[5].off); d.own_ptr = (const int *)(db + R[6].off); d.own_con = (const int *)(db + R[7].off);
-    d.lvl_ptr = (const int *)(db + R[8].off); d.lvl_col = (const int *)(db + R[9].off);
-    d.off_ptr = (const int *)(db + R[10].off); d.off_blk = (const int *)(db + R[11].off);
-    d.blk_col = (const int *)(db + R[12].off); d.pair_ptr = (const int *)(db + R[13].off); d.pairs = (const int *)(db + R[14].off);
-    d.row_ptr = (const int *)(db + R[15].off); d.row_lst = (const int *)(db + R[16].off);
-    d.col_ptr = (const int *)(db + R[17].off); d.col_lst = (const int *)(db + R[18].off);
-    d.lm = (EgLm *)(db + R[19].off); d.counter = (unsigned *)(db + R[20].off);
-    d.H = (double *)(db + R[21].off); d.pert = (double *)(db + R[22].off); d.errs = (double *)(db + R[23].off);
-    d.chi = (double *)(db + R[24].off); d.b = (double *)(db + R[25].off); d.L = (double *)(db + R[26].off);
-    d.rinv = (double *)(db + R[27].off); d.x = (double *)(db + R[28].off);
+    Layout L;
+    L.copy(d.est0, siw, 64 * (size_t)n);
+    L.copy(d.vpos, P.vpos.data(), 4 * P.vpos.size()); L.copy(d.eij, eij.data(), 4 * eij.size()); L.copy(d.meas, meas.data(), 8 * meas.size());
+    L.copy(d.own_blk, P.own_blk.data(), 4 * P.own_blk.size()); L.copy(d.own_ptr, P.own_ptr.data(), 4 * P.own_ptr.size());
+    L.copy(d.own_con, P.own_con.data(), 4 * P.own_con.size());
+    L.copy(d.lvl_ptr, P.lvl_ptr.data(), 4 * P.lvl_ptr.size()); L.copy(d.lvl_col, P.lvl_col.data(), 4 * P.lvl_col.size());
+    L.copy(d.off_ptr, P.off_ptr.data(), 4 * P.off_ptr.size()); L.copy(d.off_blk, P.off_blk.data(), 4 * P.off_blk.size());
+    L.copy(d.blk_col, P.blk_col.data(), 4 * P.blk_col.size());
+    L.copy(d.pair_ptr, P.pair_ptr.data(), 4 * P.pair_ptr.size()); L.copy(d.pairs, P.pairs.data(), 4 * P.pairs.size());
+    L.copy(d.row_ptr, P.row_ptr.data(), 4 * P.row_ptr.size()); L.copy(d.row_lst, P.row_lst.data(), 4 * P.row_lst.size());
+    L.copy(d.col_ptr, P.col_ptr.data(), 4 * P.col_ptr.size()); L.copy(d.col_lst, P.col_lst.data(), 4 * P.col_lst.size());
+    L.copy(d.lm, &lm0, sizeof(EgLm));
+    L.zero(d.est1, 64 * (size_t)n); L.zero(d.counter, 4);
+    L.zero(d.H, 49 * 8 * (size_t)nL);                            // (the fill blocks stay zero)
+    L.zero(d.pert, 224 * 8 * (size_t)na); L.zero(d.errs, EG_NERR * 7 * 8 * (size_t)ne); L.zero(d.chi, 8 * (size_t)ne);
+    L.zero(d.b, 7 * 8 * (size_t)na); L.zero(d.L, 49 * 8 * (size_t)nL); L.zero(d.rinv, 7 * 8 * (size_t)na); L.zero(d.x, 7 * 8 * (size_t)na);
     d.n = n; d.ne = ne; d.na = na; d.nlev = P.nlev; d.n_own = (int)P.own_blk.size(); d.fix_scale = fix_scale ? 1 : 0;
+    std::lock_guard<std::mutex> lock(eg_mu);
+    SolverCtx &c = eg_ctx;
+    c.bind();
+    L.place(c.dev.reserve(L.bytes()), c.in.reserve(L.staged()));
+    EgLm *hl = (EgLm *)c.out.reserve(sizeof(EgLm));
     hipStream_t st = c.stream;
-    SIVO_HIP(hipMemcpyAsync(db, hin, up_bytes, hipMemcpyHostToDevice, st));
-    SIVO_HIP(hipMemsetAsync(db + up_bytes, 0, total - up_bytes, st));
+    L.send(st);
     // the chi2 of the input (mode 1: current = chi_init), then the steps
     hipLaunchKernelGGL(eg_chi2_kernel, dim3(EG_GRID), dim3(EG_T), 0, st, d, 1);
     SIVO_HIP(hipGetLastError());
-    EgLm *hl = (EgLm *)c.h_out;
     // (every vertex on an edge fixed: g2o's optimize() finds nothing to optimise and returns; at most 10 trials per iteration)
     const int max_steps = na == 0 ? 0 : iterations * 10;
     int steps = 0;
@@ -863,23 +767,23 @@ static int eg_correct(const float *xyz, const int32_t *ref, int np, const double
     for (int k = 0; k < np; ++k)
         if (ref[k] < -1 || ref[k] >= n) throw std::invalid_argument("reference index out of range");
     if (np == 0) return SIVO_OK;
-    if (sivo_device_count() < 1) throw std::runtime_error("no HIP device: libsivo_hip has no CPU fallback");
+    require_device();
+    const float *d_xyz; const int *d_ref; const double *d_before, *d_after; float *d_out;
+    Layout L;
+    L.copy(d_xyz, xyz, 12 * (size_t)np); L.copy(d_ref, ref, 4 * (size_t)np);
+    L.copy(d_before, before, 64 * (size_t)n); L.copy(d_after, after, 64 * (size_t)n);
+    L.take(d_out, 12 * (size_t)np);
     std::lock_guard<std::mutex> lock(eg_mu);
-    EgCtx &c = eg_ctx();
-    const size_t bx = al256(12 * (size_t)np), br = al256(4 * (size_t)np), bs = al256(64 * (size_t)std::max(n, 1));
-    const size_t up = bx + br + 2 * bs;
-    c.reserve(up, up + bx, bx);
-    unsigned char *hin = (unsigned char *)c.h_in, *db = (unsigned char *)c.d_buf;
-    std::memcpy(hin, xyz, 12 * (size_t)np);
-    std::memcpy(hin + bx, ref, 4 * (size_t)np);
-    if (n) { std::memcpy(hin + bx + br, before, 64 * (size_t)n); std::memcpy(hin + bx + br + bs, after, 64 * (size_t)n); }
-    SIVO_HIP(hipMemcpyAsync(db, hin, up, hipMemcpyHostToDevice, c.stream));
-    hipLaunchKernelGGL(eg_correct_points_kernel, dim3((np + EG_T - 1) / EG_T), dim3(EG_T), 0, c.stream, (const float *)db,
-                       (const int *)(db + bx), np, (const double *)(db + bx + br), (const double *)(db + bx + br + bs), (float *)(db + up));
+    SolverCtx &c = eg_ctx;
+    c.bind();
+    L.place(c.dev.reserve(L.bytes()), c.in.reserve(L.staged()));
+    char *h_out = c.out.reserve(12 * (size_t)np);
+    L.send(c.stream);
+    hipLaunchKernelGGL(eg_correct_points_kernel, dim3((np + EG_T - 1) / EG_T), dim3(EG_T), 0, c.stream, d_xyz, d_ref, np, d_before, d_after, d_out);
     SIVO_HIP(hipGetLastError());
-    SIVO_HIP(hipMemcpyAsync(c.h_out, db + up, 12 * (size_t)np, hipMemcpyDeviceToHost, c.stream));
+    SIVO_HIP(hipMemcpyAsync(h_out, d_out, 12 * (size_t)np, hipMemcpyDeviceToHost, c.stream));
     SIVO_HIP(hipStreamSynchronize(c.stream));
-    std::memcpy(out, c.h_out, 12 * (size_t)np);
+    std::memcpy(out, h_out, 12 * (size_t)np);
     return SIVO_OK;
 }
 

@@ -147,7 +147,7 @@ extern "C" int sivo_hamming_matrix(const uint8_t *a, int n_a, const uint8_t *b, 
         if (n_a < 0 || n_b < 0) throw std::invalid_argument("negative size");
         if (n_a == 0 || n_b == 0) return SIVO_OK;
         if (!a || !b || !out) throw std::invalid_argument("null argument");
-        if (sivo_device_count() < 1) return fail(SIVO_ERR_RUNTIME, "no HIP device: libsivo_hip has no CPU fallback");
+        require_device();
         DevBuf<uint8_t> da((size_t)n_a * 32), db((size_t)n_b * 32);
         DevBuf<int32_t> dout((size_t)n_a * n_b);
         SIVO_HIP(hipMemcpy(da.p, a, (size_t)n_a * 32, hipMemcpyHostToDevice));
@@ -166,7 +166,7 @@ extern "C" int sivo_hamming_argmin2(const uint8_t *a, int n_a, const uint8_t *b,
         if (n_a < 0 || n_b < 0) throw std::invalid_argument("negative size");
         if (n_a == 0) return SIVO_OK;
         if (!a || !cand_off || !best_idx || !best_dist || !second_dist) throw std::invalid_argument("null argument");
-        if (sivo_device_count() < 1) return fail(SIVO_ERR_RUNTIME, "no HIP device: libsivo_hip has no CPU fallback");
+        require_device();
         const int ncand = cand_off[n_a];
         DevBuf<uint8_t> da((size_t)n_a * 32), db((size_t)n_b * 32);
         DevBuf<int32_t> doff((size_t)n_a + 1), didx((size_t)ncand), dbi(n_a), dbd(n_a), dsd(n_a), dsi(n_a);

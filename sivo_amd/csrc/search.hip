@@ -526,7 +526,7 @@ extern "C" int sivo_mframe_create(const SivoKeyPoint *keys, int n, const float *
         require(n >= 0 && (n == 0 || (keys && descriptors)), "keys / descriptors are NULL");
         require(nlevels > 0 && scale_factors && level_sigma2 && inv_level_sigma2, "scale tables are NULL");
         require(max_x > min_x && max_y > min_y, "empty image bounds");
-        if (sivo_device_count() < 1) return fail(SIVO_ERR_RUNTIME, "no HIP device: libsivo_hip has no CPU fallback");
+        require_device();
         if (device < 0) SIVO_HIP(hipGetDevice(&device));                    // -1: the calling thread's current device
         if (sivo_device_count() <= device)
             return fail(SIVO_ERR_RUNTIME, "HIP device %d is not available (%d visible): libsivo_hip has no CPU fallback", device,

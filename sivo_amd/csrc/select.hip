@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "solver_host.hpp"
 
 namespace sivo {
 
@@ -165,41 +166,6 @@ extern "C" int sivo_entropy_gate_dev(int n, const SivoKeyPoint *d_kps, const flo
 // calling thread which the kernel reads directly, and the three outputs are written straight into pinned memory: one launch, one
 // synchronisation, no allocation once the buffers fit.  The caller has synchronised with whatever produced d_entropy (the frame
 // has: it reads the class map back before it filters the keys).
-namespace {
-struct GateCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    char *h = nullptr;
-    size_t cap = 0;
-    void release() {
-        if (h) (void)hipHostFree(h);
-        if (stream) (void)hipStreamDestroy(stream);
-        h = nullptr; stream = nullptr; cap = 0;
-    }
-    ~GateCtx() { release(); }
-};
-GateCtx &gate_ctx(size_t bytes) {
-    static thread_local GateCtx c;
-    int dev = 0;
-    SIVO_HIP(hipGetDevice(&dev));
-    if (c.device != dev) {
-        c.release();
-        int lo = 0, hi = 0;          // (a dozen workgroups that a host thread waits for: ahead of whatever else the device is running)
-        SIVO_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        SIVO_HIP(hipStreamCreateWithPriority(&c.stream, hipStreamNonBlocking, hi));
-        c.device = dev;
-    }
-    if (bytes > c.cap) {
-        if (c.h) SIVO_HIP(hipHostFree(c.h));
-        c.h = nullptr; c.cap = 0;
-        const size_t cap = std::max(bytes * 2, (size_t)256 << 10);
-        SIVO_HIP(hipHostMalloc((void **)&c.h, cap, hipHostMallocDefault));
-        c.cap = cap;
-    }
-    return c;
-}
-}  // namespace
-
 extern "C" int sivo_entropy_gate_map_dev(int n, const SivoKeyPoint *kps, const float *depth, const double *xyz,
                                          const double *d_entropy, int rows, int cols, const double state_cov[36], double fx,
                                          double fy, double bl, const float *level_sigma2, int nlevels, double th, double *mi,
@@ -208,21 +174,24 @@ extern "C" int sivo_entropy_gate_map_dev(int n, const SivoKeyPoint *kps, const f
         if (n < 0) throw std::invalid_argument("negative size");
         if (n == 0) return SIVO_OK;
         if (!kps || !depth || !xyz || !d_entropy) throw std::invalid_argument("null argument");
-        if (sivo_device_count() < 1) return fail(SIVO_ERR_RUNTIME, "no HIP device: libsivo_hip has no CPU fallback");
-        const size_t N = (size_t)n, o_xyz = 0, o_mi = o_xyz + N * 24, o_red = o_mi + N * 8, o_kps = o_red + N * 8,
-                     o_depth = o_kps + N * sizeof(SivoKeyPoint), o_acc = o_depth + N * 4, total = o_acc + N;
-        GateCtx &c = gate_ctx(total);
-        std::memcpy(c.h + o_xyz, xyz, N * 24);
-        std::memcpy(c.h + o_kps, kps, N * sizeof(SivoKeyPoint));
-        std::memcpy(c.h + o_depth, depth, N * 4);
-        const int rc = sivo_entropy_gate_dev(n, (const SivoKeyPoint *)(c.h + o_kps), (const float *)(c.h + o_depth), (const double *)(c.h + o_xyz),
-                                             d_entropy, rows, cols, state_cov, fx, fy, bl, level_sigma2, nlevels, th,
-                                             (double *)(c.h + o_mi), (double *)(c.h + o_red), (uint8_t *)(c.h + o_acc), c.stream);
+        require_device();
+        // (a dozen workgroups that a host thread waits for: a high-priority stream, ahead of whatever else the device is running)
+        static thread_local SolverCtx c(true, 256 << 10, 0, 0);
+        c.bind();
+        const size_t N = (size_t)n;
+        const SivoKeyPoint *h_kps; const float *h_depth; const double *h_xyz; double *h_mi, *h_red; uint8_t *h_acc;
+        Layout L;                             // (all of it in the pinned buffer, where the kernel reads and writes it)
+        L.copy(h_xyz, xyz, N * 24); L.copy(h_kps, kps, N * sizeof(SivoKeyPoint)); L.copy(h_depth, depth, N * 4);
+        L.take(h_mi, N * 8); L.take(h_red, N * 8); L.take(h_acc, N);
+        char *h = c.in.reserve(L.bytes());
+        L.place(h, h);
+        const int rc = sivo_entropy_gate_dev(n, h_kps, h_depth, h_xyz, d_entropy, rows, cols, state_cov, fx, fy, bl, level_sigma2, nlevels, th,
+                                             h_mi, h_red, h_acc, c.stream);
         if (rc) return rc;
         SIVO_HIP(hipStreamSynchronize(c.stream));
-        if (mi) std::memcpy(mi, c.h + o_mi, N * 8);
-        if (reduction) std::memcpy(reduction, c.h + o_red, N * 8);
-        if (accept) std::memcpy(accept, c.h + o_acc, N);
+        if (mi) std::memcpy(mi, h_mi, N * 8);
+        if (reduction) std::memcpy(reduction, h_red, N * 8);
+        if (accept) std::memcpy(accept, h_acc, N);
         return SIVO_OK;
     });
 }
@@ -258,17 +227,12 @@ extern "C" int sivo_check_semantics(int n, const SivoKeyPoint *kps, const float 
         if (n < 0) throw std::invalid_argument("negative size");
         if (n == 0) return SIVO_OK;
         if (!kps || !depth || !xyz || !entropy || !confidence || !classes || !detected_class) throw std::invalid_argument("null argument");
-        if (sivo_device_count() < 1) return fail(SIVO_ERR_RUNTIME, "no HIP device: libsivo_hip has no CPU fallback");
-        struct Buf { void *p = nullptr; ~Buf() { (void)hipFree(p); } };
-        auto up = [](Buf &b, const void *src, size_t bytes) {
-            SIVO_HIP(hipMalloc(&b.p, bytes ? bytes : 1));
-            if (src) SIVO_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-        };
-        Buf dk, dd, dx, de, dc, dl, dm, dr, da;
+        require_device();
+        CallBuf dk, dd, dx, de, dc, dl, dm, dr, da;
         const size_t px = (size_t)rows * cols;
-        up(dk, kps, (size_t)n * sizeof(SivoKeyPoint)); up(dd, depth, (size_t)n * 4); up(dx, xyz, (size_t)n * 24);
-        up(de, entropy, px * 8); up(dc, confidence, px * 8); up(dl, classes, px);
-        up(dm, nullptr, (size_t)n * 8); up(dr, nullptr, (size_t)n * 8); up(da, nullptr, (size_t)n);
+        dk.up(kps, (size_t)n * sizeof(SivoKeyPoint)); dd.up(depth, (size_t)n * 4); dx.up(xyz, (size_t)n * 24);
+        de.up(entropy, px * 8); dc.up(confidence, px * 8); dl.up(classes, px);
+        dm.up(nullptr, (size_t)n * 8); dr.up(nullptr, (size_t)n * 8); da.up(nullptr, (size_t)n);
         const int rc = sivo_check_semantics_dev(n, (const SivoKeyPoint *)dk.p, (const float *)dd.p, (const double *)dx.p, (const double *)de.p,
                                                 (const double *)dc.p, (const uint8_t *)dl.p, rows, cols, state_cov, fx, fy, bl, level_sigma2,
                                                 nlevels, th_entropy, th_confidence, (double *)dm.p, (double *)dr.p, (uint8_t *)da.p, nullptr);
@@ -288,16 +252,11 @@ extern "C" int sivo_entropy_gate(int n, const SivoKeyPoint *kps, const float *de
         if (n < 0) throw std::invalid_argument("negative size");
         if (n == 0) return SIVO_OK;
         if (!kps || !depth || !xyz || !entropy) throw std::invalid_argument("null argument");
-        if (sivo_device_count() < 1) return fail(SIVO_ERR_RUNTIME, "no HIP device: libsivo_hip has no CPU fallback");
-        struct Buf { void *p = nullptr; ~Buf() { (void)hipFree(p); } };
-        auto up = [](Buf &b, const void *src, size_t bytes) {
-            SIVO_HIP(hipMalloc(&b.p, bytes ? bytes : 1));
-            if (src) SIVO_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-        };
-        Buf dk, dd, dx, de, dm, dr, da;
-        up(dk, kps, (size_t)n * sizeof(SivoKeyPoint)); up(dd, depth, (size_t)n * 4); up(dx, xyz, (size_t)n * 24);
-        up(de, entropy, (size_t)rows * cols * 8);
-        up(dm, nullptr, (size_t)n * 8); up(dr, nullptr, (size_t)n * 8); up(da, nullptr, (size_t)n);
+        require_device();
+        CallBuf dk, dd, dx, de, dm, dr, da;
+        dk.up(kps, (size_t)n * sizeof(SivoKeyPoint)); dd.up(depth, (size_t)n * 4); dx.up(xyz, (size_t)n * 24);
+        de.up(entropy, (size_t)rows * cols * 8);
+        dm.up(nullptr, (size_t)n * 8); dr.up(nullptr, (size_t)n * 8); da.up(nullptr, (size_t)n);
         const int rc = sivo_entropy_gate_dev(n, (const SivoKeyPoint *)dk.p, (const float *)dd.p, (const double *)dx.p,
                                              (const double *)de.p, rows, cols, state_cov, fx, fy, bl, level_sigma2, nlevels, th,
                                              (double *)dm.p, (double *)dr.p, (uint8_t *)da.p, nullptr);

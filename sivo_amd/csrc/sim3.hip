@@ -25,13 +25,13 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <stdexcept>
 #include <vector>
 
 #include "common.hpp"
 #include "sim3_common.hpp"
 #include "solver_common.hpp"
+#include "solver_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -295,21 +295,11 @@ __global__ __launch_bounds__(S3_THREADS) void sim3_optimize_kernel(Sim3Args a) {
                     chi += r;
                 });
                 const double chi_sum = red.sum1(chi);
-                const double temp = ok ? chi_sum : DBL_MAX;
-                const double rho = (current - temp) / (scale + 1e-3);
-                if (rho > 0 && isfinite(temp)) {
-                    const double t = 2 * rho - 1;
-                    double alpha = 1. - t * t * t;
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2; current = temp;
-                } else {
-                    lambda *= ni; ni *= 2;
-                    S = Sb;
-                }
+                const LmTrial tr = lm_trial(current, ok ? chi_sum : DBL_MAX, scale, lambda, ni);
+                if (!tr.accepted) S = Sb;
                 ++qmax; ++trials;
-                cont = (rho < 0 && qmax < 10);
-                term = (qmax == 10 || rho == 0);
+                cont = (tr.rho < 0 && qmax < 10);
+                term = (qmax == 10 || tr.rho == 0);
             } while (cont);
             ++iters;
             if (term) break;
@@ -356,64 +346,6 @@ static_assert(s3_lds_bytes(S3_CAP) <= 160 * 1024, "the LDS copy of the pairs mus
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// Per-thread state of the entry points (a loop closure evaluates its candidates on the loop-closing thread): one pinned staging
-// buffer for the upload and one for the results, the device buffers they go to and come from, a stream of its own.  Grow-only,
-// released when the thread exits: nothing is allocated in a call once the buffers fit.
-struct Sim3Ctx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    void *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
-    size_t cap_in = 0, cap_out = 0;
-    void release() {
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-        if (d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-        if (stream) (void)hipStreamDestroy(stream);
-        h_in = h_out = d_in = d_out = nullptr; stream = nullptr; cap_in = cap_out = 0;
-    }
-    ~Sim3Ctx() { release(); }
-    void reserve(size_t in_bytes, size_t out_bytes) {
-        if (in_bytes > cap_in) {
-            if (h_in) SIVO_HIP(hipHostFree(h_in));
-            if (d_in) SIVO_HIP(hipFree(d_in));
-            h_in = d_in = nullptr; cap_in = 0;
-            const size_t cap = std::max(in_bytes * 2, (size_t)256 << 10);
-            SIVO_HIP(hipHostMalloc(&h_in, cap, hipHostMallocDefault));
-            SIVO_HIP(hipMalloc(&d_in, cap));
-            cap_in = cap;
-        }
-        if (out_bytes > cap_out) {
-            if (h_out) SIVO_HIP(hipHostFree(h_out));
-            if (d_out) SIVO_HIP(hipFree(d_out));
-            h_out = d_out = nullptr; cap_out = 0;
-            const size_t cap = std::max(out_bytes * 2, (size_t)64 << 10);
-            SIVO_HIP(hipHostMalloc(&h_out, cap, hipHostMallocDefault));
-            SIVO_HIP(hipMalloc(&d_out, cap));
-            cap_out = cap;
-        }
-    }
-};
-static Sim3Ctx &sim3_ctx() {
-    static thread_local Sim3Ctx c;
-    int dev = 0;
-    SIVO_HIP(hipGetDevice(&dev));
-    if (c.device != dev) {
-        c.release();
-        int lo = 0, hi = 0;
-        SIVO_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        SIVO_HIP(hipStreamCreateWithPriority(&c.stream, hipStreamNonBlocking, hi));
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lock(mu);
-        SIVO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sim3_optimize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)s3_lds_bytes(S3_CAP)));
-        c.device = dev;
-    }
-    return c;
-}
-
-static size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
-
 static int sim3_run(SivoSim3Problem *probs, int k) {
     if (k < 0 || k > (1 << 20)) throw std::invalid_argument("problem count out of range");
     if (k > 0 && !probs) throw std::invalid_argument("null argument");
@@ -431,15 +363,24 @@ static int sim3_run(SivoSim3Problem *probs, int k) {
     if (total > (int64_t)1 << 26) throw std::invalid_argument("pair count out of range");
     for (int i = 0; i < k; ++i) { probs[i].n_inliers = 0; probs[i].iterations = 0; probs[i].trials = 0; }
     if (k == 0) return SIVO_OK;
-    if (sivo_device_count() < 1) throw std::runtime_error("no HIP device: libsivo_hip has no CPU fallback");
-    Sim3Ctx &c = sim3_ctx();
-    // upload: the problem headers, then every problem's pairs back to back; results: S3_OUT doubles per problem, 2 chi2 doubles and
-    // one flag byte per pair.  One copy each way, one launch, one synchronisation.
-    const size_t hdr = align64(sizeof(Sim3Prob) * (size_t)k), in_bytes = hdr + (size_t)total * sizeof(SivoSim3Match);
-    const size_t out_res = align64((size_t)k * S3_OUT * 8), out_chi = align64((size_t)total * 16), out_bytes = out_res + out_chi + (size_t)total;
-    c.reserve(in_bytes, out_bytes);
-    unsigned char *hin = (unsigned char *)c.h_in;
-    Sim3Prob *hp = (Sim3Prob *)hin;
+    require_device();
+    // a loop closure evaluates its candidates on the loop-closing thread: one pinned buffer for the upload and the results, kept per thread
+    static thread_local SolverCtx c(true, 256 << 10, 0, 256 << 10);
+    c.bind();
+    static int once[64];
+    if (FirstUse first(once); first)
+        SIVO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sim3_optimize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)s3_lds_bytes(S3_CAP)));
+    // upload: the problem headers, then every problem's pairs back to back (staged in place); results: S3_OUT doubles per problem, 2 chi2
+    // doubles and one flag byte per pair.  One copy each way, one launch, one synchronisation.
+    Sim3Args a;
+    Layout L;
+    L.copy(a.prob, nullptr, sizeof(Sim3Prob) * (size_t)k);
+    L.copy(a.pairs, nullptr, (size_t)total * sizeof(SivoSim3Match));
+    L.take(a.out, (size_t)k * S3_OUT * 8); L.take(a.chi2, (size_t)total * 16); L.take(a.outlier, (size_t)total);
+    L.place(c.dev.reserve(L.bytes()), c.in.reserve(L.bytes()));
+    Sim3Prob *hp = L.host(a.prob);
+    unsigned char *hm = (unsigned char *)L.host(a.pairs);
     int64_t off = 0;
     for (int i = 0; i < k; ++i) {
         const SivoSim3Problem &p = probs[i];
@@ -448,25 +389,17 @@ static int sim3_run(SivoSim3Problem *probs, int k) {
         q.delta = (double)std::sqrt(p.th2);                  // const float deltaHuber = sqrt(th2) (Optimizer.cc:1290): float sqrt
         q.th2 = (double)p.th2;
         q.off = off; q.n = p.n; q.fix_scale = p.fix_scale ? 1 : 0;
-        if (p.n) std::memcpy(hin + hdr + (size_t)off * sizeof(SivoSim3Match), p.matches, (size_t)p.n * sizeof(SivoSim3Match));
+        if (p.n) std::memcpy(hm + (size_t)off * sizeof(SivoSim3Match), p.matches, (size_t)p.n * sizeof(SivoSim3Match));
         off += p.n;
     }
-    Sim3Args a;
-    unsigned char *din = (unsigned char *)c.d_in, *dout = (unsigned char *)c.d_out;
-    a.prob = (const Sim3Prob *)din;
-    a.pairs = (const double *)(din + hdr);
-    a.out = (double *)dout;
-    a.chi2 = (double *)(dout + out_res);
-    a.outlier = dout + out_res + out_chi;
     a.lds_cap = std::max(1, std::min(max_n, S3_CAP));
-    SIVO_HIP(hipMemcpyAsync(c.d_in, c.h_in, in_bytes, hipMemcpyHostToDevice, c.stream));
+    L.send(c.stream);
     hipLaunchKernelGGL(sim3_optimize_kernel, dim3(k), dim3(S3_THREADS), s3_lds_bytes(a.lds_cap), c.stream, a);
     SIVO_HIP(hipGetLastError());
-    SIVO_HIP(hipMemcpyAsync(c.h_out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+    SIVO_HIP(hipMemcpyAsync(L.host(a.out), a.out, L.results(), hipMemcpyDeviceToHost, c.stream));
     SIVO_HIP(hipStreamSynchronize(c.stream));
-    const unsigned char *hout = (const unsigned char *)c.h_out;
-    const double *res = (const double *)hout, *chi = (const double *)(hout + out_res);
-    const uint8_t *flag = hout + out_res + out_chi;
+    const double *res = L.host(a.out), *chi = L.host(a.chi2);
+    const uint8_t *flag = L.host(a.outlier);
     for (int i = 0; i < k; ++i) {
         SivoSim3Problem &p = probs[i];
         const double *r = res + S3_OUT * (size_t)i;

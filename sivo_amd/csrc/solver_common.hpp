@@ -11,6 +11,25 @@ __device__ __forceinline__ void huber(double c2, double delta, double &rho, doub
     else { const double s = sqrt(c2); rho = 2 * s * delta - dsqr; w = delta / s; }
 }
 
+// g2o's OptimizationAlgorithmLevenberg::solve after one trial of chi2 `temp` (DBL_MAX when the system could not be solved): rho from the
+// chi2 `current` of the linearisation point and computeScale's `scale`; an accepted trial (rho > 0, temp finite) becomes `current` and
+// shrinks lambda, a rejected one grows lambda by ni and doubles ni.  The cube is t * t * t where g2o calls pow(t, 3), in every solver.
+struct LmTrial { double rho; bool accepted; };
+__device__ __forceinline__ LmTrial lm_trial(double &current, double temp, double scale, double &lambda, double &ni) {
+    const double rho = (current - temp) / (scale + 1e-3);
+    const bool accepted = rho > 0 && isfinite(temp);
+    if (accepted) {
+        const double t = 2 * rho - 1;
+        double alpha = 1. - t * t * t;
+        alpha = fmin(alpha, 2. / 3.);
+        lambda *= fmax(1. / 3., alpha);
+        ni = 2; current = temp;
+    } else {
+        lambda *= ni; ni *= 2;
+    }
+    return {rho, accepted};
+}
+
 // x from lane (lane ^ M) for M = 1, 2, 8 on the VALU's data-parallel crossbar (no LDS traffic); 4, 16, 32 through ds_bpermute
 template <int M>
 __device__ __forceinline__ double lane_xor(double x) {
