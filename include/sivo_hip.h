@@ -639,6 +639,44 @@ typedef struct {
 int sivo_sim3_optimize_batch(SivoSim3Problem *problems, int n_problems);
 
 /* ---------------------------------------------------------------------------
+ * Sim3Solver's RANSAC (Sim3Solver.cc), the step of LoopClosing::ComputeSim3 in front
+ * of OptimizeSim3: every hypothesis of every loop candidate in one launch.  Per
+ * hypothesis: Horn's closed form on the three sampled pairs (ComputeSim3, :224-349),
+ * then CheckInliers (:352-372) over all pairs: a pair is an inlier when both squared
+ * reprojection errors (Project, :387-409, against FromCameraToImage, :411-429) are
+ * below its thresholds.  CV_32F arithmetic with OpenCV's rounding; cv::eigen is a
+ * fixed-sweep cyclic Jacobi in double and atan2 + cv::Rodrigues the rotation matrix of
+ * the quaternion.  Results are bit-identical run to run and between the
+ * single and the batched call.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    float x1c[3], x2c[3];         /* mvX3Dc1[i], mvX3Dc2[i] (:96, :99) */
+    float max_err1, max_err2;     /* (float) mvnMaxError1[i], mvnMaxError2[i]: (unsigned long)(9.210 * sigma2) (:86-89) */
+} SivoSim3Pair;                   /* 32 bytes */
+
+typedef struct {
+    const SivoSim3Pair *pairs;
+    int32_t n;
+    float k1[4], k2[4];           /* fx fy cx cy */
+    const int32_t *triples;       /* 3 n_hyp indices into pairs, as drawn (:166-180) */
+    int32_t n_hyp;
+    int32_t min_inliers, fix_scale;
+    /* out, all caller-owned: */
+    int32_t *count;               /* n_hyp: mnInliersi of each hypothesis */
+    float *T;                     /* 13 n_hyp: R12 row-major, t12, s12 (mR12i, mt12i, ms12i); a NaN is stored as 0x7FC00000 */
+    uint64_t *inlier_bits;        /* n_hyp * ceil(n / 64) words, bit p%64 of word p/64 = mvbInliersi[p] */
+    int32_t first_accept, best;   /* first h with count > min_inliers (-1: none); last h attaining the running
+                                   * maximum under >= (:186-200; -1 without hypotheses) */
+} SivoSim3RansacProblem;
+
+/* A triple index out of range or repeated inside a triple, n < 3 with n_hyp > 0, or a NULL
+ * array with a non-zero count -> SIVO_ERR_INVALID_ARGUMENT before any device is touched.
+ * n_problems == 0, or n_hyp == 0 everywhere: no launch. */
+int sivo_sim3_ransac_batch(SivoSim3RansacProblem *problems, int n_problems);
+/* The batch of one. */
+int sivo_sim3_ransac(SivoSim3RansacProblem *problem);
+
+/* ---------------------------------------------------------------------------
  * Optimizer::OptimizeEssentialGraph from the point the graph is built
  * (Optimizer.cc:928-1180: the graph of :964-1175, then optimize(20)): one
  * VertexSim3Expmap per keyframe, EdgeSim3 edges with information I7 and no robust

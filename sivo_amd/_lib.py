@@ -72,6 +72,16 @@ class Sim3Problem(C.Structure):  # == SivoSim3Problem (one problem of sivo_sim3_
                 ("iterations", C.c_int32), ("trials", C.c_int32)]
 
 
+class Sim3Pair(C.Structure):  # == SivoSim3Pair (32 bytes): one correspondence of sivo_sim3_ransac
+    _fields_ = [("x1c", C.c_float * 3), ("x2c", C.c_float * 3), ("max_err1", C.c_float), ("max_err2", C.c_float)]
+
+
+class Sim3RansacProblem(C.Structure):  # == SivoSim3RansacProblem (one problem of sivo_sim3_ransac_batch)
+    _fields_ = [("pairs", C.c_void_p), ("n", C.c_int32), ("k1", C.c_float * 4), ("k2", C.c_float * 4), ("triples", C.c_void_p),
+                ("n_hyp", C.c_int32), ("min_inliers", C.c_int32), ("fix_scale", C.c_int32), ("count", C.c_void_p), ("T", C.c_void_p),
+                ("inlier_bits", C.c_void_p), ("first_accept", C.c_int32), ("best", C.c_int32)]
+
+
 class Sim3Edge(C.Structure):   # == SivoSim3Edge (72 bytes): one EdgeSim3 of sivo_essential_graph_optimize
     _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("meas", C.c_double * 8)]
 
@@ -158,6 +168,8 @@ SIGNATURES = {
     "sivo_pose_optimize": [_vp, _vp, _i, _vp, _i64, C.POINTER(_d), _vp, _vp, _vp, C.POINTER(_i), _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "sivo_sim3_optimize": [_vp, C.POINTER(_d), C.POINTER(_d), _vp, _i, _f, _i, _vp, C.POINTER(_i), _vp, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_sim3_optimize_batch": [_vp, _i],
+    "sivo_sim3_ransac_batch": [_vp, _i],
+    "sivo_sim3_ransac": [_vp],
     "sivo_essential_graph_optimize": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_essential_graph_analyze": [_vp, _i, _vp, _i, _vp],
     "sivo_sim3_correct_points": [_vp, _vp, _i, _vp, _vp, _i, _vp],
