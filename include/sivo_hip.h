@@ -677,6 +677,51 @@ int sivo_sim3_ransac_batch(SivoSim3RansacProblem *problems, int n_problems);
 int sivo_sim3_ransac(SivoSim3RansacProblem *problem);
 
 /* ---------------------------------------------------------------------------
+ * PnPsolver's EPnP RANSAC (PnPsolver.cc), the step of Tracking::Relocalization
+ * (Tracking.cc:1279-1330) between SearchByBoW and PoseOptimization: every hypothesis of
+ * every candidate keyframe in one launch, then every Refine in a second one.  Per
+ * hypothesis: compute_pose (:482-531) on the four sampled correspondences, then
+ * CheckInliers (:318-347) over all of them.  A hypothesis is a RECORD when its count is
+ * >= min_inliers and strictly above every earlier count and best_in: the iterations at
+ * which iterate (:228-241) replaces mvbBestInliers.  Refine (:271-315) is a pure function
+ * of mvbBestInliers, so only records are refined: compute_pose on the record's inliers,
+ * CheckInliers again.  Arithmetic in double as the source has it; cvSVD / cvSolve /
+ * cvInvert are a fixed-sweep Jacobi, the source's own qr_solve and the adjugate (DESIGN
+ * 3.6d).  Results are bit-identical run to run and between the single and the batched call.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    float xw[3];                  /* mvP3Dw[i] (:103) */
+    float u, v;                   /* mvP2D[i] (:99) */
+    float max_err;                /* mvMaxError[i] = mvSigma2[i] * th2 (:172) */
+} SivoPnpPoint;                   /* 24 bytes */
+
+typedef struct {
+    const SivoPnpPoint *points;
+    int32_t n;
+    float K[4];                   /* fx fy cx cy */
+    int32_t min_inliers;          /* mRansacMinInliers, >= 4 */
+    int32_t best_in;              /* mnBestInliers on entry: 0 for a fresh solver */
+    const int32_t *samples;       /* 4 n_hyp indices into points, as drawn (:203-220) */
+    int32_t n_hyp;
+    /* out, all caller-owned: */
+    int32_t *count;               /* n_hyp: mnInliersi of each hypothesis */
+    float *T;                     /* 12 n_hyp: mRi row-major, mti, converted CV_64F -> CV_32F (:234-237); a NaN is 0x7FC00000 */
+    uint64_t *inlier_bits;        /* n_hyp * ceil(n / 64) words, bit p%64 of word p/64 = mvbInliersi[p] */
+    int32_t *refined;             /* n_hyp: mnRefinedInliers of a record, -1 where the hypothesis is no record */
+    float *refined_T;             /* 12 n_hyp: row h written where refined[h] >= 0 */
+    uint64_t *refined_bits;       /* n_hyp * ceil(n / 64): row h written where refined[h] >= 0 (mvbRefinedInliers) */
+    int32_t n_records;            /* out */
+} SivoPnpRansacProblem;
+
+/* A sample index out of range or repeated inside a sample, n < 4 or min_inliers < 4 with
+ * n_hyp > 0, or a NULL array with a non-zero count -> SIVO_ERR_INVALID_ARGUMENT before any
+ * device is touched.  n_problems == 0, or n_hyp == 0 everywhere: no launch.  No record
+ * anywhere: no second launch. */
+int sivo_pnp_ransac_batch(SivoPnpRansacProblem *problems, int n_problems);
+/* The batch of one. */
+int sivo_pnp_ransac(SivoPnpRansacProblem *problem);
+
+/* ---------------------------------------------------------------------------
  * Optimizer::OptimizeEssentialGraph from the point the graph is built
  * (Optimizer.cc:928-1180: the graph of :964-1175, then optimize(20)): one
  * VertexSim3Expmap per keyframe, EdgeSim3 edges with information I7 and no robust

@@ -82,6 +82,16 @@ class Sim3RansacProblem(C.Structure):  # == SivoSim3RansacProblem (one problem o
                 ("inlier_bits", C.c_void_p), ("first_accept", C.c_int32), ("best", C.c_int32)]
 
 
+class PnpPoint(C.Structure):  # == SivoPnpPoint (24 bytes): one correspondence of sivo_pnp_ransac
+    _fields_ = [("xw", C.c_float * 3), ("u", C.c_float), ("v", C.c_float), ("max_err", C.c_float)]
+
+
+class PnpRansacProblem(C.Structure):  # == SivoPnpRansacProblem (one problem of sivo_pnp_ransac_batch)
+    _fields_ = [("points", C.c_void_p), ("n", C.c_int32), ("K", C.c_float * 4), ("min_inliers", C.c_int32), ("best_in", C.c_int32),
+                ("samples", C.c_void_p), ("n_hyp", C.c_int32), ("count", C.c_void_p), ("T", C.c_void_p), ("inlier_bits", C.c_void_p),
+                ("refined", C.c_void_p), ("refined_T", C.c_void_p), ("refined_bits", C.c_void_p), ("n_records", C.c_int32)]
+
+
 class Sim3Edge(C.Structure):   # == SivoSim3Edge (72 bytes): one EdgeSim3 of sivo_essential_graph_optimize
     _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("meas", C.c_double * 8)]
 
@@ -170,6 +180,8 @@ SIGNATURES = {
     "sivo_sim3_optimize_batch": [_vp, _i],
     "sivo_sim3_ransac_batch": [_vp, _i],
     "sivo_sim3_ransac": [_vp],
+    "sivo_pnp_ransac_batch": [_vp, _i],
+    "sivo_pnp_ransac": [_vp],
     "sivo_essential_graph_optimize": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_essential_graph_analyze": [_vp, _i, _vp, _i, _vp],
     "sivo_sim3_correct_points": [_vp, _vp, _i, _vp, _vp, _i, _vp],
