@@ -805,6 +805,98 @@ int sivo_check_semantics(int n, const SivoKeyPoint *kps, const float *depth, con
                          double fx, double fy, double bl, const float *level_sigma2, int nlevels, double th_entropy,
                          double th_confidence, double *mi, double *reduction, uint8_t *detected_class);
 
+/* ===========================================================================
+ * LocalMapping::CreateNewMapPoints, the body of the loop over the matches
+ * (reference src/orbslam/LocalMapping.cc:277-470) for ONE keyframe pair: the
+ * parallax test (:289-319), the linear triangulation (:320-338) or the stereo
+ * unprojection (:340-343, KeyFrame.cc:642-656), the depth tests (:351-362), the
+ * reprojection tests (:364-425), the scale-consistency test (:427-446) and both
+ * CheckSemantics calls (:449-452, :474-545).  One thread per match.  Float
+ * arithmetic as OpenCV 3.x does it (api/compat/cv_min.hpp); two pieces are
+ * restated, not pinned: the null vector of A (cv::SVD::compute) is
+ * the eigenvector of the smallest eigenvalue of A'A by cyclic Jacobi in double, and
+ * cos(2 atan2(mb / 2, depth)) is (d^2 - a^2) / (d^2 + a^2) in double.
+ * Results are bit-identical run to run and between the single and the batched call.
+ * ======================================================================== */
+typedef struct {
+    float Rcw[9], tcw[3];         /* GetRotation(), GetTranslation() (:210-212, :261-263) */
+    float Ow[3];                  /* GetCameraCenter() (:216, :238) */
+    float Twc[12];                /* mTwc.rowRange(0, 3), row-major 3 x 4 (KeyFrame.cc:652) */
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+    int32_t nlevels;              /* mnScaleLevels, 1 .. 16 */
+    float scale_factors[16];      /* mvScaleFactors */
+    float level_sigma2[16];       /* mvLevelSigma2 */
+} SivoTriKeyFrame;                /* 272 bytes */
+
+typedef struct {
+    float x1, y1;                 /* mvKeysSemantic[idx1].pt of the current keyframe (:281) */
+    int32_t octave1;
+    float r1, depth1;             /* mvRight[idx1] (< 0: no stereo), mvDepth[idx1] */
+    float x2, y2;                 /* the same of the neighbour (:285-286) */
+    int32_t octave2;
+    float r2, depth2;
+    double entropy1, confidence1; /* mEntropy / mConfidence of keyframe 1 at ((int) y1, (int) x1) (:479-484) */
+    uint8_t class1, class2;       /* mClasses of keyframe 1 / keyframe 2 at the truncated keypoint positions (:485) */
+    uint8_t pad_[6];
+} SivoTriMatch;                   /* 64 bytes */
+
+enum {
+    SIVO_TRI_ACCEPTED = 0,
+    SIVO_TRI_LOW_PARALLAX = 1,    /* :344-347 */
+    SIVO_TRI_W_ZERO = 2,          /* :333-335 */
+    SIVO_TRI_Z1 = 3,              /* :354-356 */
+    SIVO_TRI_Z2 = 4,              /* :360-362 */
+    SIVO_TRI_REPROJ1 = 5,         /* :378-380, :388-391 */
+    SIVO_TRI_REPROJ2 = 6,         /* :409-411, :421-424 */
+    SIVO_TRI_ZERO_DIST = 7,       /* :434-436 */
+    SIVO_TRI_SCALE = 8,           /* :443-446 */
+    SIVO_TRI_SEMANTICS = 9        /* :452 */
+};
+
+typedef struct {
+    SivoTriKeyFrame kf1, kf2;     /* mpCurrentKeyFrame, pKF2 */
+    float ratio_factor;           /* 1.5f * mfScaleFactor (:225) */
+    int32_t pad_;
+    double state_cov[36];         /* keyframe 1: GetCovariance(), row-major */
+    double th_confidence;         /* keyframe 1: mThConfidence */
+    double th_entropy;            /* keyframe 1: mThEntropyReduction */
+    const SivoTriMatch *matches;
+    int32_t n;
+    int32_t pad2_;
+    /* out, caller-owned: */
+    uint8_t *status;              /* n: SIVO_TRI_* — the `continue` that rejected the match */
+    float *wP;                    /* 3 n: the point as it stood when the match left the loop (0 for status 1 and 2); a NaN is 0x7FC00000 */
+    uint8_t *detected_class;      /* n: CheckSemantics(keyframe 1, ..., true) where the match reached it, else VOID (255) */
+} SivoTriProblem;
+
+/* An octave outside [0, nlevels), nlevels outside [1, 16], n < 0 or a NULL array with
+ * n > 0 -> SIVO_ERR_INVALID_ARGUMENT before any device is touched.  n == 0 everywhere:
+ * no launch. */
+int sivo_triangulate(SivoTriProblem *problem);
+/* Several keyframe pairs in one launch (a workgroup table). */
+int sivo_triangulate_batch(SivoTriProblem *problems, int n_problems);
+
+/* MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth
+ * (reference src/orbslam/MapPoint.cc:284-347, :368-411) for np map points at once,
+ * one wavefront per point.  Point p owns the descriptors desc[32 * desc_off[p] ..
+ * 32 * desc_off[p + 1]) — vDescriptors in the order of the walk over mObservations,
+ * bad keyframes left out (:305-310) — and the camera centres obs_ow[3 * obs_off[p] ..
+ * 3 * obs_off[p + 1]) of ALL its observations (:391-397).
+ * best_idx[p]: BestIdx (:330-341) — the first row of the N x N Hamming matrix whose
+ * median, the element (int)(0.5 (N - 1)) of the sorted row, is strictly smallest.
+ * max_dist / min_dist / normal[3 p]: mfMaxDistance, mfMinDistance, mNormalVector
+ * (:399-409) from pos = mWorldPos, ref_ow = pRefKF->GetCameraCenter(), level_scale =
+ * pRefKF->mvScaleFactors[level], last_scale = pRefKF->mvScaleFactors[nLevels - 1].
+ * flags[p]: bit 0 = no observation (both functions return early, :299-301 / :385-387:
+ * nothing of the point is written), bit 1 = no descriptor (:312-313: best_idx[p] is not
+ * written).  A NaN is stored as 0x7FC00000.
+ * np < 0, an offset array that does not start at 0 or decreases, or a NULL array with
+ * a non-zero count -> SIVO_ERR_INVALID_ARGUMENT before any device is touched. */
+enum { SIVO_MP_NO_OBSERVATION = 1, SIVO_MP_NO_DESCRIPTOR = 2 };
+int sivo_mappoint_refresh(int np, const int64_t *desc_off, const uint8_t *desc, const int64_t *obs_off, const float *obs_ow,
+                          const float *pos, const float *ref_ow, const float *level_scale, const float *last_scale,
+                          int32_t *best_idx, float *max_dist, float *min_dist, float *normal, uint8_t *flags);
+
 #ifdef __cplusplus
 }
 #endif

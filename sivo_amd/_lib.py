@@ -92,6 +92,27 @@ class PnpRansacProblem(C.Structure):  # == SivoPnpRansacProblem (one problem of 
                 ("refined", C.c_void_p), ("refined_T", C.c_void_p), ("refined_bits", C.c_void_p), ("n_records", C.c_int32)]
 
 
+class TriKeyFrame(C.Structure):  # == SivoTriKeyFrame (272 bytes): one keyframe header of sivo_triangulate
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("Twc", C.c_float * 12),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
+                ("mb", C.c_float), ("mbf", C.c_float), ("nlevels", C.c_int32), ("scale_factors", C.c_float * 16),
+                ("level_sigma2", C.c_float * 16)]
+
+
+class TriMatch(C.Structure):  # == SivoTriMatch (64 bytes): one match of sivo_triangulate
+    _fields_ = [("x1", C.c_float), ("y1", C.c_float), ("octave1", C.c_int32), ("r1", C.c_float), ("depth1", C.c_float),
+                ("x2", C.c_float), ("y2", C.c_float), ("octave2", C.c_int32), ("r2", C.c_float), ("depth2", C.c_float),
+                ("entropy1", C.c_double), ("confidence1", C.c_double), ("class1", C.c_uint8), ("class2", C.c_uint8),
+                ("pad_", C.c_uint8 * 6)]
+
+
+class TriProblem(C.Structure):  # == SivoTriProblem (one keyframe pair of sivo_triangulate_batch)
+    _fields_ = [("kf1", TriKeyFrame), ("kf2", TriKeyFrame), ("ratio_factor", C.c_float), ("pad_", C.c_int32),
+                ("state_cov", C.c_double * 36), ("th_confidence", C.c_double), ("th_entropy", C.c_double),
+                ("matches", C.c_void_p), ("n", C.c_int32), ("pad2_", C.c_int32), ("status", C.c_void_p), ("wP", C.c_void_p),
+                ("detected_class", C.c_void_p)]
+
+
 class Sim3Edge(C.Structure):   # == SivoSim3Edge (72 bytes): one EdgeSim3 of sivo_essential_graph_optimize
     _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("meas", C.c_double * 8)]
 
@@ -182,6 +203,9 @@ SIGNATURES = {
     "sivo_sim3_ransac": [_vp],
     "sivo_pnp_ransac_batch": [_vp, _i],
     "sivo_pnp_ransac": [_vp],
+    "sivo_triangulate_batch": [_vp, _i],
+    "sivo_triangulate": [_vp],
+    "sivo_mappoint_refresh": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sivo_essential_graph_optimize": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_essential_graph_analyze": [_vp, _i, _vp, _i, _vp],
     "sivo_sim3_correct_points": [_vp, _vp, _i, _vp, _vp, _i, _vp],

@@ -1,0 +1,80 @@
+// local_mapping_prog.cpp — the arithmetic of the triangulation and map-point-refresh kernels (sivo_amd/csrc/triangulate_math.hpp,
+// mappoint_math.hpp) compiled for the host: tests/test_local_mapping_host.py builds it with g++ -ffp-contract=off (once more with
+// -fsanitize=address,undefined) and compares what it writes with the numpy restatements bit for bit.  No device, no library.
+//   local_mapping_prog tri IN OUT       IN: kf1 kf2 (SivoTriKeyFrame), ratio_factor (f32), pad (4 bytes), state_cov (36 f64), th_confidence,
+//                                       th_entropy (f64), n (i64), n SivoTriMatch.  OUT: n status, n class, 3 n wP words.
+//   local_mapping_prog refresh IN OUT   IN: np (i64), desc_off, obs_off (np + 1 i64 each), descriptors (32 bytes each), camera centres
+//                                       (3 f32 each), np records pos[3] ref_ow[3] level_scale last_scale.  OUT: np best_idx (i32, -1: none),
+//                                       5 np words (max, min, normal), np flags.
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "mappoint_math.hpp"
+#include "triangulate_math.hpp"
+
+using namespace sivo;
+
+template <class T>
+static bool rd(FILE *f, T *p, size_t n) { return n == 0 || fread(p, sizeof(T), n, f) == n; }
+template <class T>
+static void wr(FILE *f, const T *p, size_t n) { if (n) fwrite(p, sizeof(T), n, f); }
+
+static int tri(FILE *in, FILE *out) {
+    SivoTriKeyFrame k[2];
+    float rf[2];
+    double cov[36], th[2];
+    int64_t n;
+    if (!rd(in, k, 2) || !rd(in, rf, 2) || !rd(in, cov, 36) || !rd(in, th, 2) || !rd(in, &n, 1) || n < 0) return 2;
+    std::vector<SivoTriMatch> m((size_t)n);
+    if (!rd(in, m.data(), (size_t)n)) return 2;
+    std::vector<uint8_t> status((size_t)n), cls((size_t)n);
+    std::vector<uint32_t> w(3 * (size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        if (m[i].octave1 < 0 || m[i].octave1 >= k[0].nlevels || m[i].octave2 < 0 || m[i].octave2 >= k[1].nlevels) return 3;
+        TrResult o;
+        tr_match(k[0], k[1], rf[0], cov, th[0], th[1], m[i], o);
+        status[i] = o.status; cls[i] = o.cls;
+        for (int c = 0; c < 3; ++c) w[3 * i + c] = tr_float_bits(o.wP[c]);
+    }
+    wr(out, status.data(), status.size()); wr(out, cls.data(), cls.size()); wr(out, w.data(), w.size());
+    return 0;
+}
+
+static int refresh(FILE *in, FILE *out) {
+    int64_t np;
+    if (!rd(in, &np, 1) || np < 0) return 2;
+    std::vector<int64_t> doff((size_t)np + 1), ooff((size_t)np + 1);
+    if (!rd(in, doff.data(), doff.size()) || !rd(in, ooff.data(), ooff.size())) return 2;
+    std::vector<uint64_t> desc(4 * (size_t)doff[np]);
+    std::vector<float> ow(3 * (size_t)ooff[np]), pt(8 * (size_t)np);
+    if (!rd(in, desc.data(), desc.size()) || !rd(in, ow.data(), ow.size()) || !rd(in, pt.data(), pt.size())) return 2;
+    std::vector<int32_t> best((size_t)np, -1);
+    std::vector<uint32_t> geom(5 * (size_t)np, 0);
+    std::vector<uint8_t> flags((size_t)np);
+    for (int64_t p = 0; p < np; ++p) {
+        const int64_t N = doff[p + 1] - doff[p], M = ooff[p + 1] - ooff[p];
+        if (M == 0) { flags[p] = SIVO_MP_NO_OBSERVATION | SIVO_MP_NO_DESCRIPTOR; continue; }
+        flags[p] = N > 0 ? 0 : SIVO_MP_NO_DESCRIPTOR;
+        int64_t key = INT64_MAX;
+        for (int64_t i = 0; i < N; ++i) {
+            const int64_t k = ((int64_t)mp_row_median(desc.data() + 4 * doff[p], N, i) << 32) | i;
+            key = k < key ? k : key;
+        }
+        if (N > 0) best[p] = (int32_t)(key & 0xFFFFFFFFll);
+        float o[5];
+        mp_normal_depth(&pt[8 * p], ow.data() + 3 * ooff[p], M, &pt[8 * p + 3], pt[8 * p + 6], pt[8 * p + 7], o);
+        for (int c = 0; c < 5; ++c) geom[5 * p + c] = tr_float_bits(o[c]);
+    }
+    wr(out, best.data(), best.size()); wr(out, geom.data(), geom.size()); wr(out, flags.data(), flags.size());
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc != 4) return 1;
+    FILE *in = fopen(argv[2], "rb"), *out = fopen(argv[3], "wb");
+    if (!in || !out) return 1;
+    const int rc = !strcmp(argv[1], "tri") ? tri(in, out) : !strcmp(argv[1], "refresh") ? refresh(in, out) : 1;
+    fclose(in);
+    return fclose(out) ? 1 : rc;
+}

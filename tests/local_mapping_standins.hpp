@@ -1,0 +1,89 @@
+// Minimal stand-ins for the SLAM data model (reference include/orbslam/{KeyFrame,MapPoint,Map}.h) as SIVO::CreateNewMapPoints /
+// SIVO::RefreshMapPoints (sivo_amd/api/orbslam/LocalMappingAdapter.h) use it: exactly the members the templates read, under the
+// reference's names.  The reference's own classes satisfy the same expressions (MapPoint with the two setters the adapter's header names).
+#pragma once
+#include <list>
+#include <map>
+#include <set>
+#include <utility>
+#include <vector>
+
+#include "orbslam/LocalMappingAdapter.h"
+
+struct LKeyFrame;
+struct LMap;
+
+template <class T>
+struct PixelMap {                    // mEntropy / mConfidence / mClasses: only the pixels a test looks up
+    std::map<std::pair<int, int>, T> v;
+    T operator()(int row, int col) const { auto it = v.find(std::make_pair(row, col)); return it == v.end() ? T() : it->second; }
+};
+struct Cov6 {
+    double v[36] = {0};
+    double operator()(int r, int c) const { return v[6 * r + c]; }
+};
+
+struct LMapPoint {
+    cv::Mat pos, normal = cv::Mat::zeros(3, 1, CV_32F), desc = cv::Mat::zeros(1, 32, CV_8UC1);
+    float maxDistance = 0, minDistance = 0;
+    bool bad = false;
+    LKeyFrame *ref = nullptr;
+    std::map<LKeyFrame *, size_t> observations;
+    LMapPoint(const cv::Mat &Pos, LKeyFrame *pRefKF, LMap *) : pos(Pos.clone()), ref(pRefKF) {}
+    bool isBad() const { return bad; }
+    int Observations() const { return (int)observations.size(); }
+    cv::Mat GetWorldPos() const { return pos; }
+    LKeyFrame *GetReferenceKeyFrame() const { return ref; }
+    std::map<LKeyFrame *, size_t> GetObservations() const { return observations; }
+    void AddObservation(LKeyFrame *kf, size_t idx) { observations[kf] = idx; }
+    void SetDistinctiveDescriptor(const cv::Mat &d) { desc = d.clone(); }
+    void SetNormalAndDepth(const cv::Mat &n, float maxd, float mind) { normal = n.clone(); maxDistance = maxd; minDistance = mind; }
+};
+
+struct LMap {
+    std::vector<LMapPoint *> points;
+    void AddMapPoint(LMapPoint *p) { points.push_back(p); }
+};
+
+struct LKeyFrame {
+    std::vector<cv::KeyPoint> mvKeysSemantic;
+    std::vector<float> mvRight, mvDepth;
+    cv::Mat mDescriptorsSemantic;
+    std::vector<LMapPoint *> mvpMapPoints;
+    cv::Mat mTcw = cv::Mat::eye(4, 4, CV_32F), mTwc = cv::Mat::eye(4, 4, CV_32F), mOw = cv::Mat::zeros(3, 1, CV_32F), mK = cv::Mat::eye(3, 3, CV_32F);
+    std::vector<float> mvScaleFactors, mvLevelSigma2, mvInvLevelSigma2;
+    float mnMinX = 0, mnMaxX = 1241, mnMinY = 0, mnMaxY = 376, fx = 1, fy = 1, cx = 0, cy = 0, invfx = 1, invfy = 1, mbf = 0, mb = 0, mfScaleFactor = 1.2f;
+    int mnScaleLevels = 8, numSemanticKeys = 0;
+    bool bad = false;
+    std::map<unsigned, std::vector<unsigned> > mFeatVec;
+    PixelMap<double> mEntropy, mConfidence;
+    PixelMap<int> mClasses;
+    double mThConfidence = 0, mThEntropyReduction = 0;
+    Cov6 cov;
+    Cov6 GetCovariance() const { return cov; }
+    bool isBad() const { return bad; }
+    LMapPoint *GetMapPoint(size_t i) const { return mvpMapPoints[i]; }
+    void AddMapPoint(LMapPoint *p, size_t i) { mvpMapPoints[i] = p; }
+    cv::Mat GetPose() const { return mTcw; }
+    cv::Mat GetPoseInverse() const { return mTwc; }
+    cv::Mat GetCameraCenter() const { return mOw; }
+    cv::Mat GetRotation() const { cv::Mat R(3, 3, CV_32F); for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R.at<float>(r, c) = mTcw.at<float>(r, c); return R; }
+    cv::Mat GetTranslation() const { cv::Mat t(3, 1, CV_32F); for (int r = 0; r < 3; ++r) t.at<float>(r, 0) = mTcw.at<float>(r, 3); return t; }
+    float ComputeSceneMedianDepth(int) const { return 10.f; }
+    // from a SivoTriKeyFrame record
+    void set(const SivoTriKeyFrame &k) {
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) mTcw.at<float>(r, c) = k.Rcw[3 * r + c];
+            mTcw.at<float>(r, 3) = k.tcw[r];
+            mOw.at<float>(r) = k.Ow[r];
+            for (int c = 0; c < 4; ++c) mTwc.at<float>(r, c) = k.Twc[4 * r + c];
+        }
+        fx = k.fx; fy = k.fy; cx = k.cx; cy = k.cy; invfx = k.invfx; invfy = k.invfy; mb = k.mb; mbf = k.mbf;
+        mK.at<float>(0, 0) = fx; mK.at<float>(1, 1) = fy; mK.at<float>(0, 2) = cx; mK.at<float>(1, 2) = cy;
+        mnScaleLevels = k.nlevels;
+        mvScaleFactors.assign(k.scale_factors, k.scale_factors + k.nlevels);
+        mvLevelSigma2.assign(k.level_sigma2, k.level_sigma2 + k.nlevels);
+        mvInvLevelSigma2.resize(k.nlevels);
+        for (int i = 0; i < k.nlevels; ++i) mvInvLevelSigma2[i] = 1.0f / mvLevelSigma2[i];
+    }
+};
