@@ -1,0 +1,195 @@
+// Stand-in for <opencv2/core/core.hpp> when the reference's PnPsolver.cc and Sim3Solver.cc are compiled for oracle/_ref
+// (OpenCV is not installed).  The CV_32F algebra and its rounding rules are those of sivo_amd/api/compat/cv_min.hpp, used
+// as they are: that header's class is included under the name MatCore, and cv::Mat here derives from it to add what the two
+// solver sources need beyond it and what OpenCV's expression templates decide:
+//   * views that can be written through: `A.copyTo(B.rowRange(..).colRange(..))`, `Pr.col(i) = P.col(i) - C` (an expression
+//     assigned to a matrix of its size and type is evaluated into the existing storage, Mat::create being a no-op there);
+//   * `O1 - s * R * O2` as the ONE gemm MatOp_GEMM::subtract makes of it (alpha = -s, C = O1, beta = 1);
+//   * convertTo from CV_64F, Mat_<float> with <<, cv::reduce (reduceC_'s order), cv::pow with the power 2 (a float product);
+//   * cv::eigen and cv::Rodrigues, which are the substitutions DESIGN.md §3.6c states (oracle/cv_primitives.cpp);
+//   * the legacy C API PnPsolver.cc uses: CvMat, cvMat, cvCreateMat / cvReleaseMat, cvmGet / cvmSet, cvSetZero, and cvMulTransposed,
+//     cvSVD, cvSolve, cvInvert as the substitutions of DESIGN.md §3.6d (oracle/cv_primitives.cpp).
+// Test infrastructure only.
+#pragma once
+#include <cassert>
+#include <cstdlib>
+#include <cstring>
+#define Mat MatCore
+#define Mat_ MatCore_
+#include "../../../../sivo_amd/api/compat/cv_min.hpp"
+#undef Mat
+#undef Mat_
+#include "../../../cv_primitives.h"
+typedef unsigned char uchar;
+
+#define CV_REDUCE_SUM 0
+#define CV_SVD 1
+#define CV_SVD_MODIFY_A 1
+#define CV_SVD_U_T 2
+
+namespace cv {
+
+class Mat;
+struct MatDiff {      // `A - B`, evaluated where it is assigned
+    MatCore a, b;
+};
+
+class Mat : public MatCore {
+ public:
+    Mat() {}
+    Mat(int r, int c, int type) : MatCore(r, c, type) {}
+    Mat(Size s, int type) : MatCore(s, type) {}
+    Mat(int r, int c, int type, void *ptr, size_t step_ = 0) : MatCore(r, c, type, ptr, step_) {}
+    Mat(const MatCore &m) : MatCore(m) {}
+    Mat(const MatScaled &e) : MatCore(e) {}
+    Mat(const MatProduct &e) : MatCore(e) {}
+    Mat(const MatDiff &e) : MatCore(e.a - e.b) {}
+    // an expression assigned to a matrix: into the existing storage where size and type agree, a new matrix otherwise
+    Mat &assign(const MatCore &v) {
+        if (data && v.rows == rows && v.cols == cols && v.type() == type()) write(v);
+        else MatCore::operator=(v);
+        return *this;
+    }
+    Mat &operator=(const MatDiff &e) { return assign(e.a - e.b); }
+    Mat &operator=(const MatScaled &e) { return assign(MatCore(e)); }
+    Mat &operator=(const MatProduct &e) { return assign(MatCore(e)); }
+    Mat row(int r) const { return MatCore::row(r); }
+    Mat col(int c) const { return MatCore::col(c); }
+    Mat rowRange(int a, int b) const { return MatCore::rowRange(a, b); }
+    Mat colRange(int a, int b) const { return MatCore::colRange(a, b); }
+    Mat clone() const { return MatCore::clone(); }
+    void copyTo(Mat &dst) const { dst.create(rows, cols, type()); dst.write(*this); }
+    void copyTo(Mat &&view) const { assert(view.rows == rows && view.cols == cols && view.type() == type()); view.write(*this); }
+    // CV_64F / CV_32F -> CV_32F: one rounding (dst may be *this)
+    void convertTo(Mat &dst, int type) const {
+        assert(type == CV_32F);
+        MatCore out(rows, cols, CV_32F);
+        for (int r = 0; r < rows; ++r)
+            for (int c = 0; c < cols; ++c) out.at<float>(r, c) = depth() == CV_64F ? (float)MatCore::at<double>(r, c) : MatCore::at<float>(r, c);
+        dst = Mat(out);
+    }
+
+ private:
+    void write(const MatCore &v) {
+        for (int r = 0; r < rows; ++r) std::memcpy(ptr(r), v.ptr(r), (size_t)cols * elemSize());
+    }
+};
+
+inline MatDiff operator-(const Mat &a, const Mat &b) { return MatDiff{a, b}; }
+inline MatProduct operator-(const Mat &c, const MatProduct &p) {
+    MatProduct q = p;
+    q.a.alpha = -q.a.alpha; q.c = c; q.beta = 1.0;
+    return q;
+}
+inline MatScaled operator/(const MatScaled &a, double s) { return MatScaled{a.m, a.transposed, a.alpha / s}; }
+
+template <class T>
+class Mat_ : public Mat {
+ public:
+    Mat_(int r, int c) : Mat(r, c, sizeof(T) == 4 ? CV_32F : CV_64F) {}
+    struct Filler {
+        Mat m;
+        int i;
+        template <class S> Filler &operator,(S v) { m.ptr<T>(i / m.cols)[i % m.cols] = T(v); ++i; return *this; }
+        operator Mat() const { return m; }
+    };
+    template <class S> Filler operator<<(S v) { Filler f{*this, 0}; f, v; return f; }
+};
+
+// reduce(src, dst, 1, CV_REDUCE_SUM) on CV_32F: reduceC_<float, float, OpAdd>: a0 = c0, a1 = c1, then four columns a step into
+// a0, a1, a0, a1, the rest into a0, and a0 + a1 at the end (three columns: (c0 + c2) + c1)
+inline void reduce(const Mat &src, Mat &dst, int dim, int op) {
+    assert(dim == 1 && op == CV_REDUCE_SUM && src.type() == CV_32F);
+    dst.create(src.rows, 1, CV_32F);
+    const int w = src.cols;
+    for (int y = 0; y < src.rows; ++y) {
+        const float *s = src.ptr<float>(y);
+        if (w == 1) { dst.at<float>(y, 0) = s[0]; continue; }
+        float a0 = s[0], a1 = s[1];
+        int i = 2;
+        for (; i <= w - 4; i += 4) { a0 = a0 + s[i]; a1 = a1 + s[i + 1]; a0 = a0 + s[i + 2]; a1 = a1 + s[i + 3]; }
+        for (; i < w; ++i) a0 = a0 + s[i];
+        dst.at<float>(y, 0) = a0 + a1;
+    }
+}
+
+// pow(src, 2, dst): an integer power of 2 is multiply(src, src, dst)
+inline void pow(const Mat &src, double power, Mat &dst) {
+    assert(power == 2.0 && src.type() == CV_32F);
+    dst.create(src.rows, src.cols, CV_32F);
+    for (int r = 0; r < src.rows; ++r)
+        for (int c = 0; c < src.cols; ++c) { const float v = src.at<float>(r, c); dst.at<float>(r, c) = v * v; }
+}
+
+// cv::eigen of the symmetric 4 x 4 CV_32F N and cv::Rodrigues: DESIGN.md §3.6c's substitutions.  The rotation matrix is formed
+// from the QUATERNION (the first eigenvector as the float evec holds it), not from the angle-axis vector Sim3Solver.cc derives from
+// it: eigen remembers that row and Rodrigues, which the source calls next, reads it.
+namespace solver_shim {
+inline float *last_quaternion() { static float q[4]; return q; }
+}
+inline bool eigen(const Mat &src, Mat &eval, Mat &evec) {
+    assert(src.rows == 4 && src.cols == 4 && src.type() == CV_32F);
+    float n[16], w[4], v[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) n[4 * r + c] = src.at<float>(r, c);
+    cvp_eigen4(n, w, v);
+    eval.create(4, 1, CV_32F);
+    evec.create(4, 4, CV_32F);
+    for (int r = 0; r < 4; ++r) {
+        eval.at<float>(r, 0) = w[r];
+        for (int c = 0; c < 4; ++c) evec.at<float>(r, c) = v[4 * r + c];
+    }
+    std::memcpy(solver_shim::last_quaternion(), v, sizeof(float) * 4);
+    return true;
+}
+inline void Rodrigues(const Mat &, Mat &dst) {
+    float r[9];
+    cvp_quaternion_rotation(solver_shim::last_quaternion(), r);
+    dst.create(3, 3, CV_32F);
+    for (int i = 0; i < 9; ++i) dst.at<float>(i / 3, i % 3) = r[i];
+}
+
+}  // namespace cv
+
+// ---- the legacy C API -------------------------------------------------------------------------------------------------------
+struct CvMat {
+    int type, step, rows, cols;
+    union { unsigned char *ptr; double *db; } data;
+    int owns;
+};
+inline CvMat cvMat(int rows, int cols, int type, void *data) {
+    assert(type == CV_64F);
+    CvMat m;
+    m.type = type; m.step = cols * (int)sizeof(double); m.rows = rows; m.cols = cols; m.data.db = static_cast<double *>(data); m.owns = 0;
+    return m;
+}
+inline CvMat *cvCreateMat(int rows, int cols, int type) {
+    CvMat *m = new CvMat(cvMat(rows, cols, type, std::malloc(sizeof(double) * (size_t)rows * (size_t)cols)));
+    m->owns = 1;
+    return m;
+}
+inline void cvReleaseMat(CvMat **m) { if (*m) { if ((*m)->owns) std::free((*m)->data.db); delete *m; *m = nullptr; } }
+inline double cvmGet(const CvMat *m, int r, int c) { return m->data.db[(size_t)r * m->cols + c]; }
+inline void cvmSet(CvMat *m, int r, int c, double v) { m->data.db[(size_t)r * m->cols + c] = v; }
+inline void cvSetZero(CvMat *m) { std::memset(m->data.db, 0, sizeof(double) * (size_t)m->rows * (size_t)m->cols); }
+// dst = src' src
+inline void cvMulTransposed(const CvMat *src, CvMat *dst, int order) {
+    assert(order == 1 && dst->rows == src->cols && dst->cols == src->cols);
+    cvp_mul_transposed(src->data.db, src->rows, src->cols, dst->data.db);
+}
+// the two uses of PnPsolver.cc: a symmetric matrix with U' only (CV_SVD_MODIFY_A | CV_SVD_U_T, V = 0), the general 3 x 3 with U and V
+inline void cvSVD(CvMat *A, CvMat *W, CvMat *U, CvMat *V, int flags) {
+    assert(A->rows == A->cols && (flags & CV_SVD_MODIFY_A));
+    if (!V) { assert(flags & CV_SVD_U_T); cvp_svd_symmetric(A->data.db, A->rows, W->data.db, U->data.db); }
+    else { assert(A->rows == 3 && !(flags & CV_SVD_U_T)); cvp_svd3(A->data.db, W->data.db, U->data.db, V->data.db); }
+}
+inline int cvSolve(const CvMat *A, const CvMat *b, CvMat *x, int method) {
+    assert(method == CV_SVD);
+    cvp_solve(A->data.db, A->rows, A->cols, b->data.db, x->data.db);
+    return 1;
+}
+inline double cvInvert(const CvMat *A, CvMat *Ainv, int method) {
+    assert(method == CV_SVD && A->rows == 3 && A->cols == 3);
+    cvp_invert3(A->data.db, Ainv->data.db);
+    return 1.0;
+}

@@ -2,6 +2,7 @@
 //   core:   the kernel's arithmetic (sivo_amd/csrc/pnp_epnp.hpp) compiled for the host with a team of one: `n K[4]`, n points
 //           (X Y Z u v max_err), `nsets`, then per set `m idx...`; per set EPnP on the set and CheckInliers over all points are
 //           printed (count, [R | t] as floats, the inlier words)
+//   core64: the same with [R | t] as the doubles the arithmetic holds (tests/test_pin_solvers.py)
 //   gather / run: SIVO::PnPsolver over minimal Frame / MapPoint stand-ins; candidates in the text form of
 //           tests/pnp_ransac_restatement.py frame_text
 //   gather: the correspondences the constructor keeps after SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991) (candidate, index in
@@ -64,7 +65,7 @@ static void read_candidate(Candidate &c) {
     c.solver.reset(new SIVO::PnPsolver(c.F, c.matches));
 }
 
-static int core() {
+static int core(bool doubles) {
     const int n = ri();
     const double K[4] = {(double)(float)rd(), (double)(float)rd(), (double)(float)rd(), (double)(float)rd()};
     std::vector<SivoPnpPoint> pts((size_t)n);
@@ -89,7 +90,10 @@ static int core() {
             }
         }
         std::printf("%d", count);
-        for (int i = 0; i < 12; ++i) std::printf(" %a", (float)(i < 9 ? w->Rs[sol][i] : w->ts[sol][i - 9]));
+        for (int i = 0; i < 12; ++i) {
+            const double v = i < 9 ? w->Rs[sol][i] : w->ts[sol][i - 9];
+            std::printf(" %a", doubles ? v : (double)(float)v);
+        }
         for (unsigned long long x : words) std::printf(" %llx", x);
         std::printf("\n");
     }
@@ -99,7 +103,7 @@ static int core() {
 int main(int argc, char **argv) {
     if (argc < 2) return 2;
     const std::string mode = argv[1];
-    if (mode == "core") return core();
+    if (mode == "core" || mode == "core64") return core(mode == "core64");
     const int nc = ri();
     std::vector<std::unique_ptr<Candidate>> cands;
     for (int k = 0; k < nc; ++k) {
