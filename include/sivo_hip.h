@@ -897,6 +897,60 @@ int sivo_mappoint_refresh(int np, const int64_t *desc_off, const uint8_t *desc, 
                           const float *pos, const float *ref_ow, const float *level_scale, const float *last_scale,
                           int32_t *best_idx, float *max_dist, float *min_dist, float *normal, uint8_t *flags);
 
+/* ===========================================================================
+ * Place recognition: the bag-of-words vocabulary and the keyframe database —
+ * DBoW2 as ORB-SLAM2 uses it (reference dependencies/DBoW2/DBoW2/TemplatedVocabulary.h,
+ * src/orbslam/KeyFrameDatabase.cc:72-322).  Only L1_NORM scoring with TF_IDF
+ * weighting (what ORBvoc.txt carries).  DESIGN 3.6f.
+ * ======================================================================== */
+typedef struct sivo_voc *sivo_voc_t;
+typedef struct sivo_bowdb *sivo_bowdb_t;
+
+/* The text format of TemplatedVocabulary::loadFromTextFile (TemplatedVocabulary.h:1338-1424): a header line
+ * `k L scoring weighting`, then one line `parent isLeaf b0 .. b31 weight` per node; node ids in file order from 1,
+ * the root is 0; word ids in file order over the leaf lines (:1408-1415).  k <= 20, L <= 10 (:1359); a header other
+ * than `k L 0 0` -> SIVO_ERR_INVALID_ARGUMENT with a text that says so.  Beyond the reference: empty lines are
+ * skipped, and a parent id that is not an earlier inner node, a parent with more than k children, a truncated line,
+ * an inner node without children or an empty file -> SIVO_ERR_INVALID_ARGUMENT.  No device is needed. */
+int sivo_voc_create_from_text(const char *path, sivo_voc_t *voc);
+/* The same from arrays: entry i describes node i + 1; n_nodes entries (the root is not one of them). */
+int sivo_voc_create(int k, int L, int64_t n_nodes, const int32_t *parent, const uint8_t *is_leaf, const uint8_t *desc,
+                    const double *weight, sivo_voc_t *voc);
+/* n_nodes: the root included (m_nodes.size()); n_words: size(). */
+int sivo_voc_info(sivo_voc_t voc, int32_t *k, int32_t *L, int64_t *n_nodes, int64_t *n_words);
+int sivo_voc_destroy(sivo_voc_t voc);
+
+/* transform(features, BowVector &, FeatureVector &, levelsup) (TemplatedVocabulary.h:1126-1194) with the descent of
+ * :1217-1259 for n descriptors of 32 bytes.  Per feature: word[i], and node[i] = the node at level L - levelsup (0 when
+ * levelsup >= L; the leaf's own id when the descent ends above that level, where the reference leaves it
+ * uninitialised).  The BowVector: *n_words pairs (bow_words ascending, bow_values); the FeatureVector in CSR form:
+ * *n_fv_nodes node ids ascending, fv_offsets (*n_fv_nodes + 1 entries), fv_features ascending within a node.  A word of
+ * weight 0 is in neither.  Values bit-identical to the reference's order of operations.  Every array holds n entries
+ * (fv_offsets n + 1).  n > SIVO_BOW_SET_CAP or levelsup < 0 -> SIVO_ERR_INVALID_ARGUMENT. */
+#define SIVO_BOW_SET_CAP 8192
+int sivo_bow_transform(sivo_voc_t voc, const uint8_t *desc, int n, int levelsup, int32_t *word, int32_t *node,
+                       int32_t *bow_words, double *bow_values, int32_t *n_words, int32_t *fv_nodes, int32_t *fv_offsets,
+                       int32_t *fv_features, int32_t *n_fv_nodes);
+/* Several sets in one call: set s owns the descriptors offsets[s] .. offsets[s + 1] and the same range of every array;
+ * its fv_offsets start at offsets[s] + s; n_words / n_fv_nodes have n_sets entries.  Equal to the single calls. */
+int sivo_bow_transform_batch(sivo_voc_t voc, const uint8_t *desc, const int64_t *offsets, int n_sets, int levelsup,
+                             int32_t *word, int32_t *node, int32_t *bow_words, double *bow_values, int32_t *n_words,
+                             int32_t *fv_nodes, int32_t *fv_offsets, int32_t *fv_features, int32_t *n_fv_nodes);
+/* KeyFrameDatabase's stored BowVectors, resident on the device.  add: n (word ascending, value) pairs -> *slot (slots
+ * count up from 0).  erase leaves a tombstone.  clear forgets every slot (the next add is slot 0). */
+int sivo_bowdb_create(sivo_voc_t voc, sivo_bowdb_t *db);
+int sivo_bowdb_add(sivo_bowdb_t db, const int32_t *words, const double *values, int n, int32_t *slot);
+int sivo_bowdb_erase(sivo_bowdb_t db, int32_t slot);
+int sivo_bowdb_clear(sivo_bowdb_t db);
+int sivo_bowdb_destroy(sivo_bowdb_t db);
+int sivo_bowdb_size(sivo_bowdb_t db, int32_t *n_slots);
+/* One launch over every slot.  Per slot: common = the number of words shared with the query (mnLoopWords /
+ * mnRelocWords, KeyFrameDatabase.cc:82-102, :211-229; 0 for a tombstone), first_word = the smallest shared word id or
+ * -1, score = L1Scoring::score (ScoringObject.cpp:23-68): the terms |v - w| - |v| - |w| of the shared words added in
+ * ascending word order, then -sum / 2.  The arrays hold *n_slots = sivo_bowdb_size entries. */
+int sivo_bowdb_query(sivo_bowdb_t db, const int32_t *q_words, const double *q_values, int nq, int32_t *common,
+                     int32_t *first_word, double *score, int32_t *n_slots);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,19 @@ SIGNATURES = {
     "sivo_triangulate_batch": [_vp, _i],
     "sivo_triangulate": [_vp],
     "sivo_mappoint_refresh": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sivo_voc_create_from_text": [C.c_char_p, C.POINTER(_vp)],
+    "sivo_voc_create": [_i, _i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_vp)],
+    "sivo_voc_info": [_vp, _pi32, _pi32, C.POINTER(_i64), C.POINTER(_i64)],
+    "sivo_voc_destroy": [_vp],
+    "sivo_bow_transform": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _pi32, _vp, _vp, _vp, _pi32],
+    "sivo_bow_transform_batch": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sivo_bowdb_create": [_vp, C.POINTER(_vp)],
+    "sivo_bowdb_add": [_vp, _vp, _vp, _i, _pi32],
+    "sivo_bowdb_erase": [_vp, C.c_int32],
+    "sivo_bowdb_clear": [_vp],
+    "sivo_bowdb_destroy": [_vp],
+    "sivo_bowdb_size": [_vp, _pi32],
+    "sivo_bowdb_query": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _pi32],
     "sivo_essential_graph_optimize": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_essential_graph_analyze": [_vp, _i, _vp, _i, _vp],
     "sivo_sim3_correct_points": [_vp, _vp, _i, _vp, _vp, _i, _vp],
