@@ -7,6 +7,9 @@
 #ifndef CVP_SWEEPS3
 #error "CVP_SWEEPS3 / CVP_SWEEPS12 / CVP_SWEEPS_SVD / CVP_SWEEPS4 come from the kernels' sources (oracle/Makefile)"
 #endif
+#ifndef CVP_SWEEPS_TRI
+#error "CVP_SWEEPS_TRI comes from sivo_amd/csrc/triangulate_math.hpp (oracle/Makefile)"
+#endif
 
 namespace {
 // the rotation that annihilates the off-diagonal entry `off` between diagonal entries lo (index p) and hi (index q): tangent,
@@ -198,6 +201,42 @@ void cvp_quaternion_rotation(const float *q, float *R) {
     R[6] = (float)(2.0 * (x * z - w * y) / n2 * f);
     R[7] = (float)(2.0 * (y * z + w * x) / n2 * f);
     R[8] = (float)((ww - xx - yy + zz) / n2 * f);
+}
+
+int cvp_sweeps_tri(void) { return CVP_SWEEPS_TRI; }
+
+void cvp_null4(const float *Af, float *e) {
+    double A[16], V[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 4; ++k) s = s + (double)Af[4 * k + i] * (double)Af[4 * k + j];
+            A[4 * i + j] = s;
+            V[4 * i + j] = i == j ? 1.0 : 0.0;
+        }
+    cvp_jacobi(A, V, 4, CVP_SWEEPS_TRI);
+    int best = 0;
+    for (int j = 1; j < 4; ++j)
+        if (A[5 * j] < A[5 * best]) best = j;
+    for (int r = 0; r < 4; ++r) e[r] = (float)V[4 * r + best];
+}
+
+void cvp_inv3f(const float *S, float *D) {
+    double s[9];
+    for (int i = 0; i < 9; ++i) { s[i] = (double)S[i]; D[i] = 0.0f; }
+    const double m00 = s[4] * s[8] - s[5] * s[7], m01 = s[3] * s[8] - s[5] * s[6], m02 = s[3] * s[7] - s[4] * s[6];
+    double d = s[0] * m00 - s[1] * m01 + s[2] * m02;
+    if (d == 0.) return;
+    d = 1. / d;
+    D[0] = (float)(m00 * d);
+    D[1] = (float)((s[2] * s[7] - s[1] * s[8]) * d);
+    D[2] = (float)((s[1] * s[5] - s[2] * s[4]) * d);
+    D[3] = (float)((s[5] * s[6] - s[3] * s[8]) * d);
+    D[4] = (float)((s[0] * s[8] - s[2] * s[6]) * d);
+    D[5] = (float)((s[2] * s[3] - s[0] * s[5]) * d);
+    D[6] = (float)(m02 * d);
+    D[7] = (float)((s[1] * s[6] - s[0] * s[7]) * d);
+    D[8] = (float)((s[0] * s[4] - s[1] * s[3]) * d);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-/* The OpenCV primitives under the reference's PnPsolver.cc and Sim3Solver.cc, as the substitutions DESIGN.md §3.6c / §3.6d
- * state, written once in plain C++ (cv_primitives.cpp) for the reference build of oracle/_ref and for tests/test_pin_solvers.py.
+/* The OpenCV primitives under the reference's PnPsolver.cc, Sim3Solver.cc and LocalMapping.cc, as the substitutions DESIGN.md §3.6c /
+ * §3.6d / §3.6e state, written once in plain C++ (cv_primitives.cpp) for the reference build of oracle/_ref and for tests/test_pin_solvers.py.
  * A third statement of them, independent of the kernels' headers and of the numpy restatements.  All matrices row-major. */
 #pragma once
 #ifdef __cplusplus
@@ -31,6 +31,15 @@ void cvp_eigen4(const float *N, float *eval, float *evec);
 void cvp_quaternion_rotation(const float *q, float *R);
 /* the sweep counts compiled in: 3 x 3, 12 x 12, one-sided, 4 x 4 */
 void cvp_sweeps(int *out4);
+/* cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) of the 4 x 4 float A of LocalMapping.cc:321-331, of which the source uses vt.row(3)
+ * alone, as the substitution DESIGN.md §3.6e states: e = the eigenvector of the smallest eigenvalue (ties to the lower index) of A'A, formed
+ * in double from the float A, after cvp_sweeps_tri() sweeps of cvp_jacobi, rounded to float */
+void cvp_null4(const float *A, float *e);
+/* cv::Mat::inv() of a 3 x 3 float matrix (LocalMapping.cc:653): determinant and cofactors in double, times 1 / det, rounded to float;
+ * the zero matrix where the determinant is zero */
+void cvp_inv3f(const float *S, float *D);
+/* the sweep count of cvp_null4, read from sivo_amd/csrc/triangulate_math.hpp */
+int cvp_sweeps_tri(void);
 #ifdef __cplusplus
 }
 #endif

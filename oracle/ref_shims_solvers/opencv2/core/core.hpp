@@ -5,6 +5,7 @@
 //   * views that can be written through: `A.copyTo(B.rowRange(..).colRange(..))`, `Pr.col(i) = P.col(i) - C` (an expression
 //     assigned to a matrix of its size and type is evaluated into the existing storage, Mat::create being a no-op there);
 //   * `O1 - s * R * O2` as the ONE gemm MatOp_GEMM::subtract makes of it (alpha = -s, C = O1, beta = 1);
+//   * Mat::inv() of a 3 x 3 float matrix, also on `K.t()` (LocalMapping.cc, through ref_shims_localmapping): cv_primitives.cpp;
 //   * convertTo from CV_64F, Mat_<float> with <<, cv::reduce (reduceC_'s order), cv::pow with the power 2 (a float product);
 //   * cv::eigen and cv::Rodrigues, which are the substitutions DESIGN.md §3.6c states (oracle/cv_primitives.cpp);
 //   * the legacy C API PnPsolver.cc uses: CvMat, cvMat, cvCreateMat / cvReleaseMat, cvmGet / cvmSet, cvSetZero, and cvMulTransposed,
@@ -44,6 +45,8 @@ class Mat : public MatCore {
     Mat(const MatScaled &e) : MatCore(e) {}
     Mat(const MatProduct &e) : MatCore(e) {}
     Mat(const MatDiff &e) : MatCore(e.a - e.b) {}
+    Mat(const Zeros &z) : MatCore(z) {}
+    Mat &operator=(const Zeros &z) { MatCore::operator=(z); return *this; }
     // an expression assigned to a matrix: into the existing storage where size and type agree, a new matrix otherwise
     Mat &assign(const MatCore &v) {
         if (data && v.rows == rows && v.cols == cols && v.type() == type()) write(v);
@@ -58,6 +61,12 @@ class Mat : public MatCore {
     Mat rowRange(int a, int b) const { return MatCore::rowRange(a, b); }
     Mat colRange(int a, int b) const { return MatCore::colRange(a, b); }
     Mat clone() const { return MatCore::clone(); }
+    // `K.t().inv()`, `K.inv()` on a 3 x 3 CV_32F matrix (LocalMapping.cc:653): cvp_inv3f
+    struct Transposed : MatScaled {
+        inline Mat inv() const;
+    };
+    Transposed t() const { Transposed e; static_cast<MatScaled &>(e) = MatCore::t(); return e; }
+    inline Mat inv() const;
     void copyTo(Mat &dst) const { dst.create(rows, cols, type()); dst.write(*this); }
     void copyTo(Mat &&view) const { assert(view.rows == rows && view.cols == cols && view.type() == type()); view.write(*this); }
     // CV_64F / CV_32F -> CV_32F: one rounding (dst may be *this)
@@ -75,6 +84,16 @@ class Mat : public MatCore {
     }
 };
 
+inline Mat Mat::inv() const {
+    assert(rows == 3 && cols == 3 && type() == CV_32F);
+    float s[9], d[9];
+    for (int i = 0; i < 9; ++i) s[i] = MatCore::at<float>(i / 3, i % 3);
+    cvp_inv3f(s, d);
+    Mat D(3, 3, CV_32F);
+    for (int i = 0; i < 9; ++i) D.MatCore::at<float>(i / 3, i % 3) = d[i];
+    return D;
+}
+inline Mat Mat::Transposed::inv() const { return Mat(static_cast<const MatScaled &>(*this)).inv(); }
 inline MatDiff operator-(const Mat &a, const Mat &b) { return MatDiff{a, b}; }
 inline MatProduct operator-(const Mat &c, const MatProduct &p) {
     MatProduct q = p;

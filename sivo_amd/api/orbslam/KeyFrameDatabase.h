@@ -45,24 +45,28 @@ class KeyFrameDatabase {
         check(sivo_bowdb_add(db_, w.data(), v.data(), (int)w.size(), &slot));
         if ((size_t)slot != kf_.size()) throw std::logic_error("KeyFrameDatabase: slots out of step");
         kf_.push_back(pKF);
-        slot_of_[pKF] = slot;
+        slots_of_[pKF].push_back(slot);
     }
 
     template <class KeyFrame>
     void erase(KeyFrame *pKF) {
         std::unique_lock<std::mutex> lock(mMutex);
-        std::map<void *, int32_t>::iterator it = slot_of_.find(pKF);
-        if (it == slot_of_.end()) return;                              // (the reference finds it in no list)
-        check(sivo_bowdb_erase(db_, it->second));
-        kf_[(size_t)it->second] = nullptr;
-        slot_of_.erase(it);
+        std::map<void *, std::vector<int32_t> >::iterator it = slots_of_.find(pKF);
+        if (it == slots_of_.end()) return;                             // (the reference finds it in no list)
+        // A keyframe added more than once stands in its lists once per add, and :56-62 take the FIRST entry out of each list: the
+        // earliest add goes, a later one keeps its place behind the keyframes added in between.
+        const int32_t slot = it->second.front();
+        check(sivo_bowdb_erase(db_, slot));
+        kf_[(size_t)slot] = nullptr;
+        it->second.erase(it->second.begin());
+        if (it->second.empty()) slots_of_.erase(it);
     }
 
     void clear() {
         std::unique_lock<std::mutex> lock(mMutex);
         check(sivo_bowdb_clear(db_));
         kf_.clear();
-        slot_of_.clear();
+        slots_of_.clear();
     }
 
     // KeyFrameDatabase.cc:72-202
@@ -210,7 +214,7 @@ class KeyFrameDatabase {
 
     sivo_bowdb_t db_ = nullptr;
     std::vector<void *> kf_;                 // slot -> keyframe (nullptr: erased); the slot is the add sequence
-    std::map<void *, int32_t> slot_of_;
+    std::map<void *, std::vector<int32_t> > slots_of_;   // the live slots of a keyframe, ascending: one per add not yet erased
     std::mutex mMutex;
 };
 

@@ -2,7 +2,7 @@
 // scene tests/test_gpu_bow.py writes: every keyframe's and frame's ComputeBoW, then a list of add / erase / clear / DetectLoopCandidates /
 // DetectRelocalizationCandidates calls.  Writes the BowVectors, every returned candidate vector in its order and, at the end, the
 // fields the detections leave in every keyframe, as text with hexadecimal floats (bit exact).
-//   bow_adapter_prog <voc.txt> <scene.bin> <out.txt>
+//   bow_adapter_prog <voc.txt> <scene.bin> <out.txt> [pin]
 //   scene: int64 levelsup, n_kf; per keyframe: int64 n, n x 32 bytes, int64 n_connected, ids, int64 n_ordered, ids;
 //          int64 n_frames; per frame: int64 n, n x 32 bytes; int64 n_ops; per op: int64 op (0 add, 1 erase, 2 loop, 3 reloc, 4 clear),
 //          int64 index, double minScore
@@ -12,6 +12,9 @@
 #include <iterator>
 
 #include "bow_standins.hpp"
+#ifdef SIVO_BOW_ON_HOST
+#include "bow_host_capi.hpp"
+#endif
 
 struct Reader {
     std::vector<char> b;
@@ -23,6 +26,16 @@ struct Reader {
     }
     int64_t i64() { int64_t v; get(&v, 8); return v; }
     double f64() { double v; get(&v, 8); return v; }
+    template <class T>
+    bool vector_kind(T &x) {                                            // pin scripts: true when the record was a BowVector
+        if (i64() == 0) return false;
+        std::vector<int32_t> w((size_t)i64());
+        std::vector<double> v(w.size());
+        get(w.data(), 4 * w.size());
+        get(v.data(), 8 * v.size());
+        for (size_t i = 0; i < w.size(); ++i) x.mBowVec[(DBoW2::WordId)w[i]] = v[i];
+        return true;
+    }
     cv::Mat desc() {
         const int64_t n = i64();
         cv::Mat m((int)n, 32, CV_8UC1);
@@ -54,7 +67,8 @@ static void print_bow(std::FILE *f, const char *tag, size_t i, const DBoW2::BowV
 }
 
 int main(int argc, char **argv) {
-    if (argc != 4) return 64;
+    if (argc != 4 && !(argc == 5 && std::string(argv[4]) == "pin")) return 64;
+    const bool pin = argc == 5;
     try {
         SIVO::ORBVocabulary voc;
         if (!voc.loadFromTextFile(argv[1])) return 2;
@@ -70,17 +84,19 @@ int main(int argc, char **argv) {
         for (size_t i = 0; i < kfs.size(); ++i) {
             BKeyFrame &k = kfs[i];
             k.mnId = i;
-            k.mDescriptorsSemantic = r.desc();
+            const bool given = pin && r.vector_kind(k);
+            if (!given) k.mDescriptorsSemantic = r.desc();
             for (int64_t n = r.i64(); n > 0; --n) k.connected.insert(&kfs[(size_t)r.i64()]);
             for (int64_t n = r.i64(); n > 0; --n) k.ordered.push_back(&kfs[(size_t)r.i64()]);
-            compute_bow(voc, k, levelsup, i % 2 == 0);
+            if (!given) compute_bow(voc, k, levelsup, i % 2 == 0);
             print_bow(out, "B", i, k.mBowVec, k.mFeatVec);
         }
         std::vector<BFrame> frames((size_t)r.i64());
         for (size_t i = 0; i < frames.size(); ++i) {
             frames[i].mnId = 1000 + i;
-            frames[i].mDescriptorsSemantic = r.desc();
-            compute_bow(voc, frames[i], levelsup, i % 2 == 1);
+            const bool given = pin && r.vector_kind(frames[i]);
+            if (!given) frames[i].mDescriptorsSemantic = r.desc();
+            if (!given) compute_bow(voc, frames[i], levelsup, i % 2 == 1);
             print_bow(out, "F", i, frames[i].mBowVec, frames[i].mFeatVec);
         }
         SIVO::KeyFrameDatabase db(voc);
@@ -94,13 +110,17 @@ int main(int argc, char **argv) {
             else if (op == 2) got = db.DetectLoopCandidates(&kfs[(size_t)idx], (float)min_score);
             else if (op == 3) { std::vector<BKeyFrame *> v = db.DetectRelocalizationCandidates(&frames[(size_t)idx]); got = v; }
             else if (op == 4) db.clear();
+            if (pin) std::fprintf(out, "S %lld\n", (long long)o);
             if (op == 2 || op == 3) {
                 std::fprintf(out, "Q %lld %zu", (long long)o, got.size());
                 for (size_t i = 0; i < got.size(); ++i) std::fprintf(out, " %lu", got[i]->mnId);
                 std::fprintf(out, "\n");
             }
+            for (size_t i = 0; pin && i < kfs.size(); ++i)
+                std::fprintf(out, "K %zu %lu %d %lu %d %a %a\n", i, kfs[i].mnLoopQuery, kfs[i].mnLoopWords, kfs[i].mnRelocQuery, kfs[i].mnRelocWords,
+                             (double)kfs[i].mLoopScore, (double)kfs[i].mRelocScore);
         }
-        for (size_t i = 0; i < kfs.size(); ++i)
+        for (size_t i = 0; !pin && i < kfs.size(); ++i)
             std::fprintf(out, "K %zu %lu %d %lu %d %a %a\n", i, kfs[i].mnLoopQuery, kfs[i].mnLoopWords, kfs[i].mnRelocQuery, kfs[i].mnRelocWords,
                          (double)kfs[i].mLoopScore, (double)kfs[i].mRelocScore);
         std::fclose(out);

@@ -13,7 +13,17 @@
 //   a map: neighbours (i64), checks (i64), state_cov (36 f64), th_confidence, th_entropy (f64), then the current keyframe and every neighbour:
 //          SivoTriKeyFrame, keys (i64), per key x y (f32) octave (i32) r depth (f32) class (i32) entropy confidence (f64) node (i32) pad (i32),
 //          then 32 descriptor bytes per key.
+//   prog pinwalk IN OUT       (device) a map, then monocular (i64) and one f32 per neighbour (what its ComputeSceneMedianDepth returns): the loop
+//                             over the neighbours with the scripted search of oracle/ref_localmapping_driver.cpp's `walk` (key i of the
+//                             current keyframe pairs with key n - 1 - i of the neighbour where both slots are free and i % (neighbour + 2)
+//                             == 1; during the search of the `checks`-th searched neighbour a keyframe arrives, so checkNewKeyFrames()
+//                             says yes from then on) and SIVO::TriangulateMatches.  OUT in that program's layout: per searched neighbour
+//                             neighbour (i64), F12 (9 f32), one byte per slot of the current keyframe (occupied at the search), pairs (i64),
+//                             the pairs (2 i64 each), points (i64), per point idx1 idx2 (i64), then per point pos[3] (f32).
+//   Built with -DSIVO_LM_ON_HOST, sivo_triangulate / sivo_mappoint_refresh are tests/local_mapping_host_capi.hpp (the host build of the
+//   kernels' arithmetic): the modes marked (device) then need none.
 //   prog refresh IN OUT       (device) IN as `local_mapping_prog refresh` reads it, then one byte per observation (1: its keyframe is bad).
+//                             A point's reference keyframe is the observation whose camera centre equals the record's ref_ow.
 //                             OUT per point: max, min, normal[3] (f32), descriptor (32 bytes).
 #include <cstdio>
 #include <cstring>
@@ -21,6 +31,9 @@
 #include <vector>
 
 #include "local_mapping_standins.hpp"
+#ifdef SIVO_LM_ON_HOST
+#include "local_mapping_host_capi.hpp"
+#endif
 
 template <class T>
 static bool rd(FILE *f, T *p, size_t n) { return n == 0 || fread(p, sizeof(T), n, f) == n; }
@@ -186,6 +199,57 @@ static int walk(FILE *in, FILE *out) {
     return 0;
 }
 
+static int pinwalk(FILE *in, FILE *out) {
+    MapScene s;
+    if (!s.read(in)) return 2;
+    int64_t monocular;
+    if (!rd(in, &monocular, 1)) return 2;
+    for (LKeyFrame *k : s.neigh)
+        if (!rd(in, &k->medianDepth, 1)) return 2;
+    LKeyFrame *cur = &s.kf[0];
+    const size_t n = cur->mvpMapPoints.size();
+    LMap map;
+    std::list<LMapPoint *> recent;
+    int64_t searched = 0;
+    bool arrived = false;
+    SIVO::local_mapping_detail::walk_neighbours(
+        cur, s.neigh, monocular != 0, [&] { return arrived; },
+        [&](LKeyFrame *pKF2, const cv::Mat &F12, std::vector<std::pair<size_t, size_t> > &pairs) {
+            const int64_t k = pKF2 - &s.kf[1];
+            for (size_t i = 0; i < n; ++i)
+                if (!cur->mvpMapPoints[i] && !pKF2->mvpMapPoints[n - 1 - i] && i % (size_t)(k + 2) == 1) pairs.push_back(std::make_pair(i, n - 1 - i));
+            if (++searched == s.checks) arrived = true;
+            wr(out, &k, 1);
+            for (int r = 0; r < 3; ++r) wr(out, F12.ptr<float>(r), 3);
+            std::vector<uint8_t> occupied(n);
+            for (size_t i = 0; i < n; ++i) occupied[i] = cur->mvpMapPoints[i] != nullptr;
+            wr(out, occupied.data(), n);
+        },
+        [&](LKeyFrame *pKF2, const std::vector<std::pair<size_t, size_t> > &pairs) {
+            const int64_t np = (int64_t)pairs.size();
+            wr(out, &np, 1);
+            for (const auto &pr : pairs) {
+                const int64_t ij[2] = {(int64_t)pr.first, (int64_t)pr.second};
+                wr(out, ij, 2);
+            }
+            const int nnew = SIVO::TriangulateMatches(cur, pKF2, pairs, &map, recent);
+            std::vector<int64_t> made;
+            std::vector<float> pos;
+            for (const auto &pr : pairs) {
+                LMapPoint *p = cur->mvpMapPoints[pr.first];
+                if (!p || p != pKF2->mvpMapPoints[pr.second]) continue;
+                made.push_back((int64_t)pr.first); made.push_back((int64_t)pr.second);
+                for (int r = 0; r < 3; ++r) pos.push_back(p->pos.at<float>(r));
+            }
+            const int64_t count = (int64_t)(made.size() / 2);
+            if (count != nnew) throw std::logic_error("pinwalk: the slots and TriangulateMatches' count disagree");
+            wr(out, &count, 1); wr(out, made.data(), made.size()); wr(out, pos.data(), pos.size());
+            return nnew;
+        });
+    for (LMapPoint *p : map.points) delete p;
+    return 0;
+}
+
 static int create(FILE *in, FILE *out) {
     MapScene s;
     if (!s.read(in)) return 2;
@@ -234,7 +298,14 @@ static int refresh(FILE *in, FILE *out) {
             K.mvScaleFactors = {pt[8 * p + 6], pt[8 * p + 7]};
             mp->AddObservation(&K, 0);
         }
-        if (mp->ref) for (int r = 0; r < 3; ++r) if (mp->ref->mOw.at<float>(r) != pt[8 * p + 3 + r]) return 3;    // the reference keyframe is the first observation's
+        if (mp->ref) {             // the reference keyframe is the observation whose centre the record names: the first one, unless the scene walks
+            mp->ref = nullptr;     // a point's observations in another order than they were added in
+            for (int64_t o = ooff[p]; o < ooff[p + 1] && !mp->ref; ++o) {
+                LKeyFrame &K = kfs[(size_t)o];
+                if (K.mOw.at<float>(0) == pt[8 * p + 3] && K.mOw.at<float>(1) == pt[8 * p + 4] && K.mOw.at<float>(2) == pt[8 * p + 5]) mp->ref = &K;
+            }
+            if (!mp->ref) { delete mp; return 3; }
+        }
         if ((int64_t)d != doff[p + 1]) return 3;
         points.push_back(mp);
     }
@@ -253,7 +324,7 @@ int main(int argc, char **argv) {
     try {
         rc = !strcmp(argv[1], "gather") ? gather(in, out) : !strcmp(argv[1], "triangulate") ? triangulate(in, out)
              : !strcmp(argv[1], "refresh") ? refresh(in, out) : !strcmp(argv[1], "walk") ? walk(in, out)
-             : !strcmp(argv[1], "create") ? create(in, out) : 1;
+             : !strcmp(argv[1], "create") ? create(in, out) : !strcmp(argv[1], "pinwalk") ? pinwalk(in, out) : 1;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "%s\n", e.what());
         rc = 5;

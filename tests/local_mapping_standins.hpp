@@ -69,7 +69,8 @@ struct LKeyFrame {
     cv::Mat GetCameraCenter() const { return mOw; }
     cv::Mat GetRotation() const { cv::Mat R(3, 3, CV_32F); for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R.at<float>(r, c) = mTcw.at<float>(r, c); return R; }
     cv::Mat GetTranslation() const { cv::Mat t(3, 1, CV_32F); for (int r = 0; r < 3; ++r) t.at<float>(r, 0) = mTcw.at<float>(r, 3); return t; }
-    float ComputeSceneMedianDepth(int) const { return 10.f; }
+    float medianDepth = 10.f;                          // what ComputeSceneMedianDepth returns (a test scripts it)
+    float ComputeSceneMedianDepth(int) const { return medianDepth; }
     // from a SivoTriKeyFrame record
     void set(const SivoTriKeyFrame &k) {
         for (int r = 0; r < 3; ++r) {

@@ -77,13 +77,19 @@ def test_triangulate_equals_the_restatement_bit_for_bit(name):
         assert (m["octave1"] == 7).all() and (m["octave2"] == 7).all()
 
 
-def test_triangulate_batch_equals_the_single_calls_and_repeats():
-    from sivo_amd import local_mapping as LM
+def batch_problems():
+    """The six problems of one sivo_triangulate_batch call (tests/local_mapping_pin_cases.py feeds the same six to the reference)."""
     probs = [TR.make_problem(60, 130, min_margin=0), TR.make_problem(61, 1, min_margin=0, stereo=(1.0, 1.0)),
              TR.make_problem(62, 64, min_margin=0, intr=(500.0, 510.0, 320.0, 240.0), mbf=200.0, nlevels=5),
              TR.make_problem(63, 0, min_margin=0), TR.make_problem(64, 65, min_margin=0, stereo=(0.0, 1.0), mbf2=300.0),
              TR.make_problem(65, 333, min_margin=0, nlevels=3)]
     probs[2]["th_confidence"], probs[4]["th_confidence"] = 0.8, 0.0
+    return probs
+
+
+def test_triangulate_batch_equals_the_single_calls_and_repeats():
+    from sivo_amd import local_mapping as LM
+    probs = batch_problems()
     assert len({len(p["matches"]) for p in probs}) == 6 and len({p["th_entropy"] for p in probs}) >= 5
     singles = [run(p) for p in probs]
     batch = LM.triangulate_batch(probs)
