@@ -503,6 +503,7 @@ int sivo_search_for_triangulation(int n_nodes, const int32_t *off1, const int32_
  * cull.  Left/right keypoints and descriptors are host arrays; the pyramids
  * are those of two sivo_orb handles' last extraction (still in HBM).
  * u_right / depth: n_left floats, -1 where unmatched. */
+/* sivo_stereo_match: a left or right key whose octave is outside [0, nlevels) of the extractors -> SIVO_ERR_INVALID_ARGUMENT, no output written. */
 int sivo_stereo_match(sivo_orb_t left, sivo_orb_t right, const SivoKeyPoint *kp_left, const uint8_t *desc_left,
                       int n_left, const SivoKeyPoint *kp_right, const uint8_t *desc_right, int n_right,
                       float bf, float b, float *u_right, float *depth, int32_t *best_right);
@@ -512,6 +513,7 @@ int sivo_stereo_match(sivo_orb_t left, sivo_orb_t right, const SivoKeyPoint *kp_
  * SAD distance of each match (sad_dist, -1 where unmatched); `cull` then applies the median test over the
  * keypoints with keep[i] != 0 (NULL = all) and clears the others.  begin + cull(keep) == sivo_stereo_match on
  * the kept subset. */
+/* sivo_stereo_match_begin: the keys' octaves are scanned first; one outside [0, nlevels) -> SIVO_ERR_INVALID_ARGUMENT, no output written. */
 int sivo_stereo_match_begin(sivo_orb_t left, sivo_orb_t right, const SivoKeyPoint *kp_left, const uint8_t *desc_left,
                             int n_left, const SivoKeyPoint *kp_right, const uint8_t *desc_right, int n_right,
                             float bf, float b, float *u_right, float *depth, int32_t *best_right, int32_t *sad_dist);
@@ -775,6 +777,8 @@ int sivo_sim3_correct_points(const float *xyz, const int32_t *ref, int np, const
  * the truncated keypoint position; accept iff reduction > th.
  * state_cov: 6x6 row-major (Frame::mSigmacw); level_sigma2: mvLevelSigma2.
  * ======================================================================== */
+/* sivo_entropy_gate_dev: the keys are on the device and are not scanned; a key whose octave is outside [0, nlevels) fails the gate
+ * (MI 0, reduction 0, accept 0) and level_sigma2 is not indexed with it. */
 int sivo_entropy_gate_dev(int n, const SivoKeyPoint *d_kps, const float *d_depth, const double *d_xyz,
                           const double *d_entropy, int rows, int cols, const double state_cov[36], double fx,
                           double fy, double bl, const float *level_sigma2, int nlevels, double th,
@@ -782,10 +786,12 @@ int sivo_entropy_gate_dev(int n, const SivoKeyPoint *d_kps, const float *d_depth
 /* Host key arrays against the DEVICE-resident entropy map (what sivo_segnet_segment_dev left in HBM): the form the per-frame
  * path uses — the keys come out of the semantic filter on the host, the map stays where the network wrote it.  Synchronous;
  * the caller has synchronised with the producer of d_entropy. */
+/* sivo_entropy_gate_map_dev: an octave outside [0, nlevels) -> SIVO_ERR_INVALID_ARGUMENT before anything is staged, outputs untouched. */
 int sivo_entropy_gate_map_dev(int n, const SivoKeyPoint *kps, const float *depth, const double *xyz,
                               const double *d_entropy, int rows, int cols, const double state_cov[36], double fx,
                               double fy, double bl, const float *level_sigma2, int nlevels, double th, double *mi,
                               double *reduction, uint8_t *accept);
+/* sivo_entropy_gate: an octave outside [0, nlevels) -> SIVO_ERR_INVALID_ARGUMENT before anything is staged, outputs untouched. */
 int sivo_entropy_gate(int n, const SivoKeyPoint *kps, const float *depth, const double *xyz,
                       const double *entropy, int rows, int cols, const double state_cov[36], double fx,
                       double fy, double bl, const float *level_sigma2, int nlevels, double th, double *mi,
@@ -795,11 +801,13 @@ int sivo_entropy_gate(int n, const SivoKeyPoint *kps, const float *depth, const 
  * over n keypoints: detected_class[i] = the class at the truncated keypoint position if depth > 0, the class is static
  * (<= TERRAIN = 8), confidence >= th_confidence and NOT (MI - entropy < th_entropy) — equality passes, unlike the
  * Tracking gate above — else VOID (255).  mi / reduction may be NULL. */
+/* sivo_check_semantics_dev: a key whose octave is outside [0, nlevels) fails (MI 0, reduction 0, class VOID), nothing is indexed with it. */
 int sivo_check_semantics_dev(int n, const SivoKeyPoint *d_kps, const float *d_depth, const double *d_xyz,
                              const double *d_entropy, const double *d_confidence, const uint8_t *d_classes, int rows, int cols,
                              const double state_cov[36], double fx, double fy, double bl, const float *level_sigma2,
                              int nlevels, double th_entropy, double th_confidence, double *d_mi, double *d_reduction,
                              uint8_t *d_detected_class, void *stream);
+/* sivo_check_semantics: an octave outside [0, nlevels) -> SIVO_ERR_INVALID_ARGUMENT before anything is staged, outputs untouched. */
 int sivo_check_semantics(int n, const SivoKeyPoint *kps, const float *depth, const double *xyz, const double *entropy,
                          const double *confidence, const uint8_t *classes, int rows, int cols, const double state_cov[36],
                          double fx, double fy, double bl, const float *level_sigma2, int nlevels, double th_entropy,

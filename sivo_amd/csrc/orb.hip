@@ -1350,6 +1350,12 @@ extern "C" int sivo_stereo_match_begin(sivo_orb_t left, sivo_orb_t right, const 
         if (left->nlevels != right->nlevels || left->rows != right->rows || left->cols != right->cols)
             throw std::invalid_argument("left/right extractors differ in geometry");
         if (nL && !sad_dist) throw std::invalid_argument("bad argument");
+        // scale[], inv_scale[] and table.lv[] are indexed with the keys' octaves: a key outside the extractors' levels is refused
+        // before any output is written
+        for (int i = 0; i < nL; ++i)
+            if (kpL[i].octave < 0 || kpL[i].octave >= left->nlevels) throw std::invalid_argument("left keypoint octave outside [0, nlevels)");
+        for (int i = 0; i < nR; ++i)
+            if (kpR[i].octave < 0 || kpR[i].octave >= left->nlevels) throw std::invalid_argument("right keypoint octave outside [0, nlevels)");
         for (int i = 0; i < nL; ++i) { u_right[i] = -1.f; depth[i] = -1.f; sad_dist[i] = -1; if (best_right) best_right[i] = -1; }
         if (nL == 0 || nR == 0) return SIVO_OK;
         DeviceGuard dg(left->device);

@@ -32,6 +32,7 @@ struct GateArgs {
     double Sx[36];
     double fx, fy, bl, th;
     float level_sigma2[16];
+    int nlevels;                       // a key whose octave is outside [0, nlevels) fails the gate: level_sigma2[] is never indexed with it
     double *mi, *reduction;
     uint8_t *accept;
     // CheckSemantics form (classes != nullptr): accept[] receives the detected class, or VOID (255)
@@ -47,7 +48,7 @@ __global__ void entropy_gate_kernel(GateArgs g) {
     uint8_t acc = 0;
     const SivoKeyPoint kp = g.kps[i];
     const int col = (int)kp.x, row = (int)kp.y;
-    bool ok = g.depth[i] > 0 && row >= 0 && row < g.rows && col >= 0 && col < g.cols;
+    bool ok = g.depth[i] > 0 && row >= 0 && row < g.rows && col >= 0 && col < g.cols && kp.octave >= 0 && kp.octave < g.nlevels;
     int cls = 255;
     if (g.classes) {
         acc = 255;                                                   // Classes::VOID
@@ -72,6 +73,14 @@ __global__ void entropy_gate_kernel(GateArgs g) {
 
 using namespace sivo;
 
+// Host-array entry points: every key's octave is looked at before anything is staged or launched, so that a bad one
+// leaves the outputs as they were (the device-resident forms cannot look: there the kernel fails such a key).
+static void require_octaves(const SivoKeyPoint *kps, int n, int nlevels) {
+    if (nlevels < 1 || nlevels > 16) throw std::invalid_argument("bad sizes (nlevels <= 16)");
+    for (int i = 0; i < n; ++i)
+        if (kps[i].octave < 0 || kps[i].octave >= nlevels) throw std::invalid_argument("keypoint octave outside [0, nlevels)");
+}
+
 extern "C" int sivo_entropy_gate_dev(int n, const SivoKeyPoint *d_kps, const float *d_depth, const double *d_xyz,
                                      const double *d_entropy, int rows, int cols, const double state_cov[36], double fx,
                                      double fy, double bl, const float *level_sigma2, int nlevels, double th,
@@ -85,6 +94,7 @@ extern "C" int sivo_entropy_gate_dev(int n, const SivoKeyPoint *d_kps, const flo
         for (int i = 0; i < 36; ++i) g.Sx[i] = state_cov[i];
         g.fx = fx; g.fy = fy; g.bl = bl; g.th = th;
         for (int i = 0; i < nlevels; ++i) g.level_sigma2[i] = level_sigma2[i];
+        g.nlevels = nlevels;
         g.mi = d_mi; g.reduction = d_reduction; g.accept = d_accept;
         hipLaunchKernelGGL(entropy_gate_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, g);
         SIVO_HIP(hipGetLastError());
@@ -105,6 +115,7 @@ extern "C" int sivo_entropy_gate_map_dev(int n, const SivoKeyPoint *kps, const f
         if (n < 0) throw std::invalid_argument("negative size");
         if (n == 0) return SIVO_OK;
         if (!kps || !depth || !xyz || !d_entropy) throw std::invalid_argument("null argument");
+        require_octaves(kps, n, nlevels);
         require_device();
         // (a dozen workgroups that a host thread waits for: a high-priority stream, ahead of whatever else the device is running)
         static thread_local SolverCtx c(true, 256 << 10, 0, 0);
@@ -142,6 +153,7 @@ extern "C" int sivo_check_semantics_dev(int n, const SivoKeyPoint *d_kps, const 
         for (int i = 0; i < 36; ++i) g.Sx[i] = state_cov[i];
         g.fx = fx; g.fy = fy; g.bl = bl; g.th = th_entropy;
         for (int i = 0; i < nlevels; ++i) g.level_sigma2[i] = level_sigma2[i];
+        g.nlevels = nlevels;
         g.mi = d_mi; g.reduction = d_reduction; g.accept = d_detected_class;
         g.confidence = d_confidence; g.classes = d_classes; g.th_conf = th_confidence;
         hipLaunchKernelGGL(entropy_gate_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, g);
@@ -158,6 +170,7 @@ extern "C" int sivo_check_semantics(int n, const SivoKeyPoint *kps, const float 
         if (n < 0) throw std::invalid_argument("negative size");
         if (n == 0) return SIVO_OK;
         if (!kps || !depth || !xyz || !entropy || !confidence || !classes || !detected_class) throw std::invalid_argument("null argument");
+        require_octaves(kps, n, nlevels);
         require_device();
         CallBuf dk, dd, dx, de, dc, dl, dm, dr, da;
         const size_t px = (size_t)rows * cols;
@@ -183,6 +196,7 @@ extern "C" int sivo_entropy_gate(int n, const SivoKeyPoint *kps, const float *de
         if (n < 0) throw std::invalid_argument("negative size");
         if (n == 0) return SIVO_OK;
         if (!kps || !depth || !xyz || !entropy) throw std::invalid_argument("null argument");
+        require_octaves(kps, n, nlevels);
         require_device();
         CallBuf dk, dd, dx, de, dm, dr, da;
         dk.up(kps, (size_t)n * sizeof(SivoKeyPoint)); dd.up(depth, (size_t)n * 4); dx.up(xyz, (size_t)n * 24);
