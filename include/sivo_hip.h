@@ -400,6 +400,9 @@ int sivo_mframe_create(const SivoKeyPoint *keys, int n, const float *u_right, co
                        const float *level_sigma2, const float *inv_level_sigma2, int nlevels, int device,
                        sivo_mframe_t *out);
 int sivo_mframe_destroy(sivo_mframe_t h);
+/* The size of the device slab that holds the frame's arrays and the scratch of its searches.  A search that needs more moves the
+ * frame to a bigger slab; tests read this to see that one did. */
+int sivo_mframe_slab_bytes(sivo_mframe_t h, int64_t *bytes);
 /* Frame::GetFeaturesInArea (Frame.cc:326-390) from that grid, host side, in the reference's order. */
 int sivo_mframe_features_in_area(sivo_mframe_t h, float x, float y, float r, int min_level, int max_level,
                                  int32_t *out, int capacity, int *n_out);
@@ -904,6 +907,65 @@ enum { SIVO_MP_NO_OBSERVATION = 1, SIVO_MP_NO_DESCRIPTOR = 2 };
 int sivo_mappoint_refresh(int np, const int64_t *desc_off, const uint8_t *desc, const int64_t *obs_off, const float *obs_ow,
                           const float *pos, const float *ref_ow, const float *level_scale, const float *last_scale,
                           int32_t *best_idx, float *max_dist, float *min_dist, float *normal, uint8_t *flags);
+
+/* ===========================================================================
+ * Tracking::SearchLocalPoints (reference src/orbslam/Tracking.cc:1033-1085): the
+ * local map culled with Frame::isInFrustum (Frame.cc:267-324, with
+ * MapPoint::PredictScale, MapPoint.cc:439-453), then matched with
+ * ORBmatcher::SearchByProjection(Frame &, const vector<MapPoint *> &, th).
+ * One thread per map point; DESIGN 3.6g.
+ * ======================================================================== */
+typedef struct {
+    float Rcw[9], tcw[3];          /* mTcw, row-major; mOw is derived from them */
+    float fx, fy, cx, cy, bf;      /* bf = mbf */
+    float min_x, max_x, min_y, max_y; /* mnMinX .. mnMaxY */
+    float log_scale_factor;        /* mfLogScaleFactor = logf(mfScaleFactor), > 0 */
+    int32_t nlevels;               /* mnScaleLevels, 1 .. 16 */
+    float cos_limit;               /* viewingCosLimit (Tracking passes 0.5) */
+} SivoFrustum;                     /* 96 bytes */
+
+enum {
+    SIVO_FRUSTUM_IN_VIEW = 0,
+    SIVO_FRUSTUM_BEHIND = 1,       /* Frame.cc:280 PcZ < 0 */
+    SIVO_FRUSTUM_U = 2,            /* :288 u outside [mnMinX, mnMaxX] */
+    SIVO_FRUSTUM_V = 3,            /* :290 v outside [mnMinY, mnMaxY] */
+    SIVO_FRUSTUM_DISTANCE = 4,     /* :299 outside [0.8 min_dist, 1.2 max_dist] */
+    SIVO_FRUSTUM_ANGLE = 5,        /* :308 viewCos < cos_limit */
+    SIVO_FRUSTUM_SKIPPED = 6       /* skip[i] != 0: isBad() or mnLastFrameSeen == the frame's id (Tracking.cc:1057-1063) */
+};
+
+/* isInFrustum for n map points: pos = mWorldPos, normal = mNormalVector (3 n each),
+ * min_dist / max_dist = mfMinDistance / mfMaxDistance (NOT the *Invariance getters:
+ * the factors 0.8f and 1.2f are applied inside), skip (n bytes) may be NULL.
+ * status[i] = SIVO_FRUSTUM_*, the `return false` the point took.  proj_x, proj_y,
+ * proj_xr, view_cos and level receive mTrackProjX, mTrackProjY, mTrackProjXR,
+ * mTrackViewCos and mnTrackScaleLevel of the points IN VIEW; the entries of every
+ * other point are left as the caller had them.  *n_in_view = the number of status 0.
+ * nlevels outside [1, 16], log_scale_factor <= 0, n < 0 or a NULL array with n > 0
+ * -> SIVO_ERR_INVALID_ARGUMENT before any device is touched. */
+int sivo_frustum_cull(const SivoFrustum *frustum, int n, const float *pos, const float *normal, const float *min_dist,
+                      const float *max_dist, const uint8_t *skip, uint8_t *status, float *proj_x, float *proj_y,
+                      float *proj_xr, float *view_cos, int32_t *level, int *n_in_view);
+/* The same on device arrays (the frustum itself is a host struct), asynchronous on
+ * `stream`; d_n_in_view (one int32 on the device) may be NULL. */
+int sivo_frustum_cull_dev(const SivoFrustum *frustum, int n, const float *d_pos, const float *d_normal,
+                          const float *d_min_dist, const float *d_max_dist, const uint8_t *d_skip, uint8_t *d_status,
+                          float *d_proj_x, float *d_proj_y, float *d_proj_xr, float *d_view_cos, int32_t *d_level,
+                          int32_t *d_n_in_view, void *stream);
+/* The second loop of Tracking::SearchLocalPoints and the search behind it in one
+ * call: the points travel in the search engine's one upload, a kernel culls them and
+ * writes the query of every point in view on the device, and the engine's rounds run
+ * on those.  mp_desc (32 n) = GetDescriptor(), mp_obs (n) = Observations(); th,
+ * nn_ratio, occ_obs (in/out) and match (out) as sivo_search_by_projection_mappoints.
+ * status (n) as sivo_frustum_cull; proj_x .. level may each be NULL and are written
+ * for the points in view only.  *n_to_match = nToMatch (the points in view),
+ * *n_matches = what SearchByProjection returns (0 when nothing is in view: the
+ * reference then skips the search).  frustum->nlevels must not exceed the frame's. */
+int sivo_search_local_points(sivo_mframe_t F, const SivoFrustum *frustum, int n, const float *pos, const float *normal,
+                             const float *min_dist, const float *max_dist, const uint8_t *skip, const uint8_t *mp_desc,
+                             const int32_t *mp_obs, float th, float nn_ratio, int32_t *occ_obs, int32_t *match,
+                             uint8_t *status, float *proj_x, float *proj_y, float *proj_xr, float *view_cos, int32_t *level,
+                             int *n_to_match, int *n_matches);
 
 /* ===========================================================================
  * Place recognition: the bag-of-words vocabulary and the keyframe database —

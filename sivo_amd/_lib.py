@@ -113,6 +113,12 @@ class TriProblem(C.Structure):  # == SivoTriProblem (one keyframe pair of sivo_t
                 ("detected_class", C.c_void_p)]
 
 
+class Frustum(C.Structure):  # == SivoFrustum (96 bytes): the camera of sivo_frustum_cull / sivo_search_local_points
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("bf", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("log_scale_factor", C.c_float), ("nlevels", C.c_int32), ("cos_limit", C.c_float)]
+
+
 class Sim3Edge(C.Structure):   # == SivoSim3Edge (72 bytes): one EdgeSim3 of sivo_essential_graph_optimize
     _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("meas", C.c_double * 8)]
 
@@ -175,6 +181,7 @@ SIGNATURES = {
     "sivo_hamming_bruteforce_dev": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "sivo_mframe_create": [_vp, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _i, _i, C.POINTER(_vp)],
     "sivo_mframe_destroy": [_vp],
+    "sivo_mframe_slab_bytes": [_vp, C.POINTER(_i64)],
     "sivo_mframe_features_in_area": [_vp, _f, _f, _f, _i, _i, _vp, _i, _pi32],
     "sivo_search": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _pi32, _pi32],
     "sivo_search_by_projection_mappoints": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _pi32],
@@ -206,6 +213,9 @@ SIGNATURES = {
     "sivo_triangulate_batch": [_vp, _i],
     "sivo_triangulate": [_vp],
     "sivo_mappoint_refresh": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sivo_frustum_cull": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi32],
+    "sivo_frustum_cull_dev": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sivo_search_local_points": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi32, _pi32],
     "sivo_voc_create_from_text": [C.c_char_p, C.POINTER(_vp)],
     "sivo_voc_create": [_i, _i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_vp)],
     "sivo_voc_info": [_vp, _pi32, _pi32, C.POINTER(_i64), C.POINTER(_i64)],

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "frustum_math.hpp"
 
 #define SIVO_GRID_COLS 64   // FRAME_GRID_COLS (reference include/orbslam/Frame.h:38-39)
 #define SIVO_GRID_ROWS 48
@@ -363,11 +364,27 @@ char *scratch(sivo_mframe &F, size_t bytes) {
     return F.slab->d + F.frame_bytes;
 }
 
-// The engine on host arrays: upload queries, rounds, finalize, download.
+// Queries made on the device (sivo_search_local_points): the engine carves `up_bytes` more into its upload block and `down_bytes` more
+// into its download block, the producer stages its inputs into the mirror of the former, enqueues its kernel behind the upload — it
+// writes all nq query records — and reads its own results from the mirror of the latter once the engine has synchronised.
+// Contract: with nq > 0 the engine calls stage, launch and collect, once each and in that order; with nq <= 0 it returns before it
+// takes any scratch and calls none of them (there is nothing to stage or collect).  scratch() may move the frame to a bigger slab, so
+// every device pointer of the frame (d_scale, ...) and its stream are valid only from launch on: launch takes them from the frame it
+// is handed, never from a copy made before run_search.
+struct DeviceQueries {
+    size_t up_bytes = 0, down_bytes = 0;
+    virtual void stage(char *h_up) = 0;
+    virtual void launch(const sivo_mframe &F, SivoSearchQuery *d_q, char *d_up, char *d_down) = 0;
+    virtual void collect(const char *h_down) = 0;
+    virtual ~DeviceQueries() {}
+};
+
+// The engine on host arrays: upload queries, rounds, finalize, download.  With `dq` the queries come from the device and `queries` is
+// not read; without it nothing of the layout or the launches changes.
 void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *query_desc, int nq, const int32_t *cand_begin,
                 const int32_t *cand_end, const int32_t *cand_idx, int n_cand, const SivoSearchRule &rule, const uint8_t *blocked,
                 int32_t *match_query, int32_t *match_train, int32_t *best_dist, int32_t *second_dist, int *n_matches,
-                int *rounds_out) {
+                int *rounds_out, DeviceQueries *dq = nullptr) {
     if (rounds_out) *rounds_out = 0;
     if (n_matches) *n_matches = 0;
     if (match_train) for (int k = 0; k < F.n; ++k) match_train[k] = -1;
@@ -381,7 +398,7 @@ void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *q
     DeviceGuard dg(F.device);
     const int n = F.n;
     const size_t need = 256 * 20 + (size_t)nq * (sizeof(SivoSearchQuery) + 32 + 8 + 4 * 4) + (size_t)(cand_idx ? n_cand : 0) * 4 +
-                        (size_t)(n + 64) * (1 + 4 * 4) + 1024;
+                        (size_t)(n + 64) * (1 + 4 * 4) + 1024 + (dq ? dq->up_bytes + dq->down_bytes + 512 : 0);
     // Scratch = [ upload block | device-only | download block ], the pinned mirror has the same layout: ONE copy up (queries,
     // their descriptors, candidate lists, blocked flags and the initial values of pick / owner / npick / flags), one copy down.
     char *const d0 = scratch(F, need);
@@ -395,18 +412,21 @@ void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *q
     int32_t *d_pick = carve<int32_t>(p, nq);
     int32_t *d_owner0 = carve<int32_t>(p, rule.dynamic ? n : 0), *d_npick = carve<int32_t>(p, rule.dynamic ? n : 0);
     int32_t *d_flags = carve<int32_t>(p, 4);     // collision, changed, accepted, culled
+    char *d_dq_up = carve<char>(p, dq ? dq->up_bytes : 0);
     const size_t up_bytes = (size_t)(p - d0);
     int32_t *d_owner1 = carve<int32_t>(p, rule.dynamic ? n : 0);
     if (!rule.dynamic) d_npick = carve<int32_t>(p, n);
     char *const down0 = p;
     int32_t *d_counters = carve<int32_t>(p, 4);
     int32_t *d_mq = carve<int32_t>(p, nq), *d_mtrain = carve<int32_t>(p, n), *d_bd = carve<int32_t>(p, nq), *d_sd = carve<int32_t>(p, nq);
+    char *d_dq_down = carve<char>(p, dq ? dq->down_bytes : 0);
     const size_t down_bytes = (size_t)(p - down0);
     int32_t *d_owner[2] = {d_owner0, d_owner1};
     auto host = [&](auto *dev) { return reinterpret_cast<std::remove_reference_t<decltype(*dev)> *>(h0 + ((char *)dev - d0)); };
     hipStream_t st = F.stream;
     SIVO_HIP(hipStreamSynchronize(st));          // (the mirror may still feed the frame's own upload)
-    std::memcpy(host(d_q), queries, (size_t)nq * sizeof(SivoSearchQuery));
+    if (dq) dq->stage(host(d_dq_up));
+    else std::memcpy(host(d_q), queries, (size_t)nq * sizeof(SivoSearchQuery));
     std::memcpy(host(d_qdesc), query_desc, (size_t)nq * 32);
     if (cand_idx) {
         std::memcpy(host(d_cbeg), cand_begin, (size_t)nq * 4);
@@ -421,6 +441,7 @@ void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *q
     }
     std::memset(host(d_flags), 0, 16);
     SIVO_HIP(hipMemcpyAsync(d0, h0, up_bytes, hipMemcpyHostToDevice, st));
+    if (dq) dq->launch(F, d_q, d_dq_up, d_dq_down);
 
     SearchArgs a{};
     a.n = n; a.x = F.d_x; a.y = F.d_y; a.angle = F.d_angle; a.ur = F.u_right.empty() ? nullptr : F.d_ur;
@@ -464,6 +485,7 @@ void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *q
     if (second_dist) std::memcpy(second_dist, host(d_sd), (size_t)nq * 4);
     if (n_matches) *n_matches = cnt[0] - cnt[1];
     if (rounds_out) *rounds_out = rounds;
+    if (dq) dq->collect(host(d_dq_down));
 }
 
 // Frame::GetFeaturesInArea (Frame.cc:326-390) on the host copy of the grid.
@@ -508,6 +530,106 @@ SivoSearchRule make_rule(int th, int gate_mode, int ratio_mode, float nn, bool o
 void require(bool ok, const char *what) {
     if (!ok) throw std::invalid_argument(what);
 }
+
+// ---- Tracking::SearchLocalPoints: the cull and the queries of the points in view, on the device --------------------------------
+// One thread per map point: Frame::isInFrustum (frustum_math.hpp, the function frustum.hip runs), then the query record exactly as
+// sivo_search_by_projection_mappoints builds it on the host, written straight into the engine's query block; a point that is not in
+// view leaves a zeroed record (flags 0: the round kernel skips it).
+struct FrQueryArgs {
+    FrCamera cam;
+    int n;
+    float th;
+    const float *pos, *normal, *min_dist, *max_dist;
+    const uint8_t *skip;           // may be null
+    const int32_t *obs;
+    const float *scale;            // the frame's mvScaleFactors (cam.f.nlevels <= the frame's levels)
+    SivoSearchQuery *q;
+    uint8_t *status;
+    float *px, *py, *pxr, *vc;     // written for the points in view only
+    int32_t *level;
+};
+
+__global__ __launch_bounds__(256) void fr_queries_kernel(FrQueryArgs a) {
+    const int i = blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= a.n) return;
+    uint8_t st = SIVO_FRUSTUM_SKIPPED;
+    FrResult o;
+    if (!(a.skip && a.skip[i])) {
+        const float X[3] = {a.pos[3 * (int64_t)i], a.pos[3 * (int64_t)i + 1], a.pos[3 * (int64_t)i + 2]};
+        const float N[3] = {a.normal[3 * (int64_t)i], a.normal[3 * (int64_t)i + 1], a.normal[3 * (int64_t)i + 2]};
+        st = fr_point(a.cam, X, N, a.min_dist[i], a.max_dist[i], o);
+    }
+    SivoSearchQuery q;
+    if (st == SIVO_FRUSTUM_IN_VIEW) {
+        fr_query(o, a.th, a.scale, a.obs[i], q);
+        a.px[i] = o.u; a.py[i] = o.v; a.pxr[i] = o.ur; a.vc[i] = o.view_cos; a.level[i] = o.level;
+    } else {
+        fr_no_query(q);
+    }
+    a.q[i] = q;
+    a.status[i] = st;
+}
+
+struct LocalPointQueries : DeviceQueries {
+    FrQueryArgs a;
+    size_t N;
+    const float *pos, *normal, *min_dist, *max_dist;      // the caller's host arrays
+    const uint8_t *skip;
+    const int32_t *obs;
+    uint8_t *status;
+    float *px, *py, *pxr, *vc;                             // each may be null
+    int32_t *level;
+    int n_to_match = 0;
+    static size_t al(size_t bytes) { return (bytes + 255) / 256 * 256; }
+    explicit LocalPointQueries(size_t n) : N(n) {
+        up_bytes = 2 * al(12 * N) + 3 * al(4 * N) + al(N);
+        down_bytes = al(N) + 5 * al(4 * N);
+    }
+    void stage(char *h) override {
+        std::memcpy(h, pos, 12 * N); h += al(12 * N);
+        std::memcpy(h, normal, 12 * N); h += al(12 * N);
+        std::memcpy(h, min_dist, 4 * N); h += al(4 * N);
+        std::memcpy(h, max_dist, 4 * N); h += al(4 * N);
+        std::memcpy(h, obs, 4 * N); h += al(4 * N);
+        if (skip) std::memcpy(h, skip, N);
+    }
+    void launch(const sivo_mframe &F, SivoSearchQuery *d_q, char *u, char *d) override {
+        a.scale = F.d_scale;                                       // (after scratch(): the frame may have moved to a bigger slab)
+        a.pos = (const float *)u; u += al(12 * N);
+        a.normal = (const float *)u; u += al(12 * N);
+        a.min_dist = (const float *)u; u += al(4 * N);
+        a.max_dist = (const float *)u; u += al(4 * N);
+        a.obs = (const int32_t *)u; u += al(4 * N);
+        a.skip = skip ? (const uint8_t *)u : nullptr;
+        a.q = d_q;
+        a.status = (uint8_t *)d; d += al(N);
+        a.px = (float *)d; d += al(4 * N);
+        a.py = (float *)d; d += al(4 * N);
+        a.pxr = (float *)d; d += al(4 * N);
+        a.vc = (float *)d; d += al(4 * N);
+        a.level = (int32_t *)d;
+        hipLaunchKernelGGL(fr_queries_kernel, dim3((unsigned)cdiv((int)N, 256)), dim3(256), 0, F.stream, a);
+        SIVO_HIP(hipGetLastError());
+    }
+    void collect(const char *h) override {
+        const uint8_t *hs = (const uint8_t *)h; h += al(N);
+        const float *hx = (const float *)h; h += al(4 * N);
+        const float *hy = (const float *)h; h += al(4 * N);
+        const float *hr = (const float *)h; h += al(4 * N);
+        const float *hc = (const float *)h; h += al(4 * N);
+        const int32_t *hl = (const int32_t *)h;
+        for (size_t i = 0; i < N; ++i) {
+            status[i] = hs[i];
+            if (hs[i] != SIVO_FRUSTUM_IN_VIEW) continue;               // nothing else of the point is written
+            ++n_to_match;
+            if (px) px[i] = hx[i];
+            if (py) py[i] = hy[i];
+            if (pxr) pxr[i] = hr[i];
+            if (vc) vc[i] = hc[i];
+            if (level) level[i] = hl[i];
+        }
+    }
+};
 
 }  // namespace
 }  // namespace sivo
@@ -595,6 +717,14 @@ extern "C" int sivo_mframe_destroy(sivo_mframe_t h) {
     });
 }
 
+extern "C" int sivo_mframe_slab_bytes(sivo_mframe_t h, int64_t *bytes) {
+    return guarded([&] {
+        require(h && bytes, "null argument");
+        *bytes = (int64_t)h->slab->cap;
+        return SIVO_OK;
+    });
+}
+
 extern "C" int sivo_mframe_features_in_area(sivo_mframe_t h, float x, float y, float r, int min_level, int max_level,
                                             int32_t *out, int capacity, int *n_out) {
     return guarded([&] {
@@ -656,6 +786,33 @@ extern "C" int sivo_search_by_projection_mappoints(sivo_mframe_t F, int n_mp, co
                    n_matches, nullptr);
         for (int k = 0; k < F->n; ++k)
             if (match[k] >= 0) occ_obs[k] = mp_obs[match[k]];
+        return SIVO_OK;
+    });
+}
+
+extern "C" int sivo_search_local_points(sivo_mframe_t F, const SivoFrustum *frustum, int n, const float *pos, const float *normal,
+                                        const float *min_dist, const float *max_dist, const uint8_t *skip, const uint8_t *mp_desc,
+                                        const int32_t *mp_obs, float th, float nn_ratio, int32_t *occ_obs, int32_t *match,
+                                        uint8_t *status, float *proj_x, float *proj_y, float *proj_xr, float *view_cos,
+                                        int32_t *level, int *n_to_match, int *n_matches) {
+    return guarded([&] {
+        require(F && frustum && n >= 0 && occ_obs && match, "null argument");
+        require(n == 0 || (pos && normal && min_dist && max_dist && mp_desc && mp_obs && status), "null argument");
+        require(frustum->nlevels >= 1 && frustum->nlevels <= 16, "nlevels outside 1 .. 16");
+        require(frustum->nlevels <= F->nlevels, "the frustum has more levels than the frame's scale tables");
+        LocalPointQueries lp((size_t)n);
+        require(fr_camera(*frustum, lp.a.cam), "log_scale_factor must be positive");
+        lp.a.n = n; lp.a.th = th; lp.a.scale = nullptr;             // (the frame's scale table: set in launch)
+        lp.pos = pos; lp.normal = normal; lp.min_dist = min_dist; lp.max_dist = max_dist; lp.skip = skip; lp.obs = mp_obs;
+        lp.status = status; lp.px = proj_x; lp.py = proj_y; lp.pxr = proj_xr; lp.vc = view_cos; lp.level = level;
+        std::vector<uint8_t> blocked((size_t)F->n);
+        for (int k = 0; k < F->n; ++k) blocked[k] = occ_obs[k] > 0;
+        const SivoSearchRule rule = make_rule(SIVO_TH_HIGH, 1, 1, nn_ratio, false, true);
+        run_search(*F, nullptr, mp_desc, n, nullptr, nullptr, nullptr, 0, rule, blocked.data(), nullptr, match, nullptr, nullptr, n_matches,
+                   nullptr, &lp);
+        for (int k = 0; k < F->n; ++k)
+            if (match[k] >= 0) occ_obs[k] = mp_obs[match[k]];
+        if (n_to_match) *n_to_match = lp.n_to_match;
         return SIVO_OK;
     });
 }

@@ -92,6 +92,12 @@ class MatchFrame:
                 pass
             self._h = None
 
+    def slab_bytes(self):
+        """The size of the device slab behind the frame (its arrays and the scratch of its searches; a bigger search grows it)."""
+        b = C.c_int64(0)
+        check(self._L.sivo_mframe_slab_bytes(self._h, C.byref(b)))
+        return b.value
+
     def features_in_area(self, x, y, r, min_level=-1, max_level=-1):
         """Frame::GetFeaturesInArea (Frame.cc:326-390)."""
         out = np.empty(self.n + 1, np.int32); n = C.c_int32(0)
