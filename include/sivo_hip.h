@@ -968,6 +968,87 @@ int sivo_search_local_points(sivo_mframe_t F, const SivoFrustum *frustum, int n,
                              int *n_to_match, int *n_matches);
 
 /* ===========================================================================
+ * Covisibility bookkeeping: KeyFrame::UpdateConnections (reference
+ * src/orbslam/KeyFrame.cc:327-415), the vote of Tracking::UpdateLocalKeyFrames
+ * (Tracking.cc:1126-1142), LocalMapping::KeyFrameCulling (LocalMapping.cc:727-792)
+ * and LocalMapping::MapPointCulling (LocalMapping.cc:165-196).  All four walk map
+ * points and their observation lists; the work is integer and exact.  DESIGN 3.6h.
+ * ======================================================================== */
+typedef struct {
+    int32_t n_kf;              /* keyframes are dense indices 0 .. n_kf-1 chosen by the caller */
+    int32_t n_points;
+    const int64_t *obs_off;    /* n_points + 1, CSR over mObservations */
+    const int32_t *obs_kf;     /* keyframe index of each observation */
+    const uint8_t *obs_level;  /* mvKeysSemantic[idx].octave of that observation */
+    const uint8_t *obs_stereo; /* mvRight[idx] >= 0 (MapPoint.cc:157, :170) */
+    const uint8_t *point_bad;  /* n_points: isBad() */
+} SivoObsTable;
+
+/* Above this many keyframes the count kernel's histogram no longer lives in LDS
+ * (32 KiB of counters) and the kernel adds into the zeroed output row instead. */
+#define SIVO_COVIS_LDS_KF 8192
+
+/* The counting loop of KeyFrame::UpdateConnections (KeyFrame.cc:340-360) and of
+ * Tracking::UpdateLocalKeyFrames (Tracking.cc:1129-1142) for n_sets slot lists in one
+ * launch.  Set s is set_point[set_off[s] .. set_off[s + 1]): mvpMapPoints of one
+ * keyframe or frame, -1 for a null slot.  counts[s * n_kf + k] = the number of slots
+ * of the set whose point is not bad and is observed by keyframe k; observations by
+ * k == set_self[s] are skipped (KeyFrame.cc:356), set_self[s] = -1 skips none
+ * (Tracking.cc:1135-1137).  A point in two slots counts twice.  Every entry of
+ * counts is written.
+ * For this and the two calls below: an offset array that does not start at 0 or
+ * that decreases, an index outside its range, a negative count or a NULL array with
+ * a non-zero count -> SIVO_ERR_INVALID_ARGUMENT before any device is touched; zero
+ * work -> no launch. */
+int sivo_covis_count(const SivoObsTable *t, int n_sets, const int64_t *set_off, const int32_t *set_point,
+                     const int32_t *set_self, int32_t *counts);
+
+enum {
+    SIVO_KFCULL_KEPT = 0,
+    SIVO_KFCULL_CULLED = 1,        /* SetBadFlag ran: the keyframe's observations left every point (KeyFrame.cc:493-495) */
+    SIVO_KFCULL_TO_BE_ERASED = 2,  /* SetBadFlag on a keyframe with mbNotErase (KeyFrame.cc:482-485): nothing changes */
+    SIVO_KFCULL_ID0 = 3            /* LocalMapping.cc:735 */
+};
+
+/* The whole loop of LocalMapping::KeyFrameCulling (LocalMapping.cc:732-791) over
+ * n_local keyframes in the caller's order, in one launch, with the reference's
+ * sequential effects: a culled, erasable keyframe's observations are removed from
+ * every point (MapPoint.cc:164-189: nObs falls by 2 for a stereo observation, else by
+ * 1; a point whose nObs is <= 2 after such a removal is bad from then on and later
+ * keyframes skip it).  Observations() of :757 is the weighted sum over the
+ * observations that are left.
+ * Local keyframe j: local_kf[j] its table index, is_id0[j] (mnId == 0), erasable[j]
+ * (!mbNotErase), th_depth[j] (mThDepth), and the slots slot_off[j] .. slot_off[j + 1]:
+ * slot_point (-1: null), slot_level (mvKeysSemantic[i].octave), slot_depth
+ * (mvDepth[i]).  The depth rule of :750-751 is evaluated as written: a NaN depth and
+ * a depth equal to th_depth are counted; monocular != 0 switches it off.
+ * Out: n_mps[j] (nMPs), n_redundant[j] (nRedundantObservations), decision[j]
+ * (SIVO_KFCULL_*; 1 and 2 where nRedundantObservations > 0.9 * nMPs in double), and
+ * bad_after[p] for every point of the table.  n_mps[j] and n_redundant[j] of a
+ * keyframe with decision 3 are left as the caller had them. */
+int sivo_keyframe_culling(const SivoObsTable *t, int n_local, const int32_t *local_kf, const uint8_t *is_id0,
+                          const uint8_t *erasable, const float *th_depth, const int64_t *slot_off,
+                          const int32_t *slot_point, const uint8_t *slot_level, const float *slot_depth, int monocular,
+                          int32_t *n_mps, int32_t *n_redundant, uint8_t *decision, uint8_t *bad_after);
+
+enum {
+    SIVO_MPCULL_STAYS = 0,         /* LocalMapping.cc:192-194 */
+    SIVO_MPCULL_ALREADY_BAD = 1,   /* :181-182 */
+    SIVO_MPCULL_FOUND_RATIO = 2,   /* :183-185, SetBadFlag */
+    SIVO_MPCULL_OBSERVATIONS = 3,  /* :186-189, SetBadFlag */
+    SIVO_MPCULL_AGED_OUT = 4       /* :190-191 */
+};
+
+/* The branch of LocalMapping::MapPointCulling (LocalMapping.cc:181-194) each of the n
+ * recently added points takes, one thread per point: found = mnFound, visible =
+ * mnVisible (the ratio is (float)found / visible < 0.25f in float, MapPoint.cc:281),
+ * first_kf_id = mnFirstKFid, n_obs = Observations(), bad = isBad(); current_kf_id =
+ * mpCurrentKeyFrame->mnId (both ids are cast to int before the subtraction, :186);
+ * the threshold on n_obs is 2 when monocular, else 3.  status[i] = SIVO_MPCULL_*. */
+int sivo_mappoint_culling(int n, const int32_t *found, const int32_t *visible, const int64_t *first_kf_id,
+                          const int32_t *n_obs, const uint8_t *bad, int64_t current_kf_id, int monocular, uint8_t *status);
+
+/* ===========================================================================
  * Place recognition: the bag-of-words vocabulary and the keyframe database —
  * DBoW2 as ORB-SLAM2 uses it (reference dependencies/DBoW2/DBoW2/TemplatedVocabulary.h,
  * src/orbslam/KeyFrameDatabase.cc:72-322).  Only L1_NORM scoring with TF_IDF

@@ -216,6 +216,9 @@ SIGNATURES = {
     "sivo_frustum_cull": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi32],
     "sivo_frustum_cull_dev": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sivo_search_local_points": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi32, _pi32],
+    "sivo_covis_count": [_vp, _i, _vp, _vp, _vp, _vp],
+    "sivo_keyframe_culling": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    "sivo_mappoint_culling": [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp],
     "sivo_voc_create_from_text": [C.c_char_p, C.POINTER(_vp)],
     "sivo_voc_create": [_i, _i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_vp)],
     "sivo_voc_info": [_vp, _pi32, _pi32, C.POINTER(_i64), C.POINTER(_i64)],
