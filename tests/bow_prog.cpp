@@ -1,6 +1,6 @@
 // bow_prog.cpp — the host build of the place-recognition arithmetic (sivo_amd/csrc/bow_math.hpp, bow_voc.hpp) as a stand-alone program:
-// tests/test_bow_host.py compares what it writes with tests/bow_restatement.py bit for bit, also under -fsanitize=address,undefined,
-// and feeds the loader malformed files.  tools/bow_probe.py times `bench` beside the device.
+// tests/test_bow_host.py builds it through tests/host_prog.py, compares what it writes with tests/bow_restatement.py bit for bit, also
+// under the sanitizers, and feeds the loader malformed files.  tools/bow_probe.py times `bench` beside the device.
 //   bow_prog load <voc.txt>                         -> "k L nodes words" on stdout; exit 2 and the message on stderr when rejected
 //   bow_prog transform <voc.txt> <in> <out>         in: int64 n_sets, levelsup; per set int64 n, n x 32 bytes
 //                                                   out: per set int64 n, nw, nf, m; word[n] node[n] bow_words[nw] fv_nodes[nf]
@@ -11,79 +11,56 @@
 //                                                   of the query against n_stored vectors of n_vec words
 #include <chrono>
 #include <cstdio>
-#include <fstream>
 #include <iostream>
 
+#include "blob_io.hpp"
 #include "bow_voc.hpp"
 
 using namespace sivo;
 
-static std::vector<char> slurp(const char *path) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) throw std::runtime_error(std::string("cannot open ") + path);
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-
-struct Reader {
-    const std::vector<char> &b;
-    size_t at = 0;
-    template <class T> void get(T *dst, size_t n) {
-        if (at + n * sizeof(T) > b.size()) throw std::runtime_error("input file too short");
-        if (n) std::memcpy(dst, b.data() + at, n * sizeof(T));
-        at += n * sizeof(T);
-    }
-    int64_t i64() { int64_t v; get(&v, 1); return v; }
-};
-
-template <class T> static void put(std::ofstream &f, const std::vector<T> &v) {
-    if (!v.empty()) f.write((const char *)v.data(), (std::streamsize)(v.size() * sizeof(T)));
-}
-
 static int run_transform(const char *voc_path, const char *in, const char *out) {
     BowVocImage img;
     bow_load_text(voc_path, img);
-    const std::vector<char> raw = slurp(in);
-    Reader r{raw};
-    const int64_t n_sets = r.i64(), levelsup = r.i64();
-    std::ofstream f(out, std::ios::binary);
+    BlobReader r(in);
+    const int64_t n_sets = r.one<int64_t>(), levelsup = r.one<int64_t>();
+    BlobWriter f;
     for (int64_t s = 0; s < n_sets; ++s) {
-        const int64_t n = r.i64();
+        const int64_t n = r.one<int64_t>();
         if (n < 0 || n > BOW_SET_CAP) throw std::runtime_error("set size out of range");
-        std::vector<uint8_t> desc(32 * (size_t)n);
-        r.get(desc.data(), desc.size());
+        const std::vector<uint8_t> desc = r.many<uint8_t>(32 * (size_t)n);
         BowSet o;
         bow_transform_host(img.view(), desc.data(), (int)n, (int)levelsup, o);
         const int64_t head[4] = {n, (int64_t)o.bow_words.size(), (int64_t)o.fv_nodes.size(), (int64_t)o.fv_feat.size()};
-        f.write((const char *)head, sizeof head);
-        put(f, o.word); put(f, o.node); put(f, o.bow_words); put(f, o.fv_nodes); put(f, o.fv_off); put(f, o.fv_feat); put(f, o.bow_values);
+        f.put(head, 4);
+        f.put(o.word); f.put(o.node); f.put(o.bow_words); f.put(o.fv_nodes); f.put(o.fv_off); f.put(o.fv_feat); f.put(o.bow_values);
     }
-    return f.good() ? 0 : 1;
+    f.save(out);
+    return 0;
 }
 
 struct Vec { std::vector<int32_t> w; std::vector<double> v; };
 
 static int run_query(const char *in, const char *out) {
-    const std::vector<char> raw = slurp(in);
-    Reader r{raw};
-    const int64_t n_slots = r.i64();
+    BlobReader r(in);
+    const int64_t n_slots = r.one<int64_t>();
     std::vector<Vec> vs((size_t)n_slots + 1);
     for (Vec &x : vs) {
-        const int64_t n = r.i64();
-        x.w.resize((size_t)n); x.v.resize((size_t)n);
-        r.get(x.w.data(), x.w.size()); r.get(x.v.data(), x.v.size());
+        const int64_t n = r.one<int64_t>();
+        x.w = r.many<int32_t>((size_t)n); x.v = r.many<double>((size_t)n);
         bow_check_vector(x.w.data(), x.v.data(), (int)n, 0x7FFFFFFF);
     }
     const Vec &q = vs.back();
-    std::ofstream f(out, std::ios::binary);
+    BlobWriter f;
     for (int64_t s = 0; s < n_slots; ++s) {
         int32_t cf[2];
         double score;
         bow_query_host(q.w.data(), q.v.data(), (int)q.w.size(), vs[(size_t)s].w.data(), vs[(size_t)s].v.data(), (int)vs[(size_t)s].w.size(), cf[0],
                        cf[1], score);
-        f.write((const char *)cf, sizeof cf);
-        f.write((const char *)&score, sizeof score);
+        f.put(cf, 2);
+        f.put(&score, 1);
     }
-    return f.good() ? 0 : 1;
+    f.save(out);
+    return 0;
 }
 
 static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
@@ -144,27 +121,23 @@ static int run_bench(int k, int L, int n, int n_stored, int n_vec) {
     return o.word.size() == (size_t)n ? 0 : 1;
 }
 
-int main(int argc, char **argv) {
-    try {
-        const std::string mode = argc > 1 ? argv[1] : "";
-        if (mode == "load" && argc == 3) {
-            BowVocImage img;
-            try {
-                bow_load_text(argv[2], img);
-            } catch (const std::invalid_argument &e) {
-                std::cerr << e.what() << "\n";
-                return 2;
-            }
-            std::printf("%d %d %d %d\n", img.k, img.L, img.n_nodes(), img.n_words);
-            return 0;
+static int run(int argc, char **argv) {
+    const std::string mode = argc > 1 ? argv[1] : "";
+    if (mode == "load" && argc == 3) {
+        BowVocImage img;
+        try {
+            bow_load_text(argv[2], img);
+        } catch (const std::invalid_argument &e) {            // a rejected file: the loader's message and 2, which the test asserts
+            std::cerr << e.what() << "\n";
+            return 2;
         }
-        if (mode == "transform" && argc == 5) return run_transform(argv[2], argv[3], argv[4]);
-        if (mode == "query" && argc == 4) return run_query(argv[2], argv[3]);
-        if (mode == "bench" && argc == 7) return run_bench(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoi(argv[6]));
-        std::cerr << "usage: bow_prog load|transform|query|bench ...\n";
-        return 64;
-    } catch (const std::exception &e) {
-        std::cerr << e.what() << "\n";
-        return 1;
+        std::printf("%d %d %d %d\n", img.k, img.L, img.n_nodes(), img.n_words);
+        return 0;
     }
+    if (mode == "transform" && argc == 5) return run_transform(argv[2], argv[3], argv[4]);
+    if (mode == "query" && argc == 4) return run_query(argv[2], argv[3]);
+    if (mode == "bench" && argc == 7) return run_bench(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoi(argv[6]));
+    throw BlobUsage();
 }
+
+int main(int argc, char **argv) { return blob_main(argc, argv, "bow_prog load|transform|query|bench ...", run); }

@@ -19,12 +19,10 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "blob_io.hpp"
 #include "covis_host_capi.hpp"
 #include "covis_standins.hpp"
 #include "CovisibilityAdapter.h"
@@ -35,34 +33,13 @@ using standin::MapPoint;
 
 namespace {
 
-struct Reader {
-    std::vector<char> buf;
-    size_t at = 0;
-    explicit Reader(const char *path) {
-        FILE *f = std::fopen(path, "rb");
-        if (!f) throw std::runtime_error("cannot open input");
-        char tmp[1 << 16];
-        size_t n;
-        while ((n = std::fread(tmp, 1, sizeof tmp, f)) > 0) buf.insert(buf.end(), tmp, tmp + n);
-        std::fclose(f);
-    }
-    template <class T> T one() { return many<T>(1)[0]; }
-    template <class T> std::vector<T> many(size_t n) {
-        std::vector<T> v(n);
-        if (at + n * sizeof(T) > buf.size()) throw std::runtime_error("input too short");
-        if (n) std::memcpy(v.data(), buf.data() + at, n * sizeof(T));
-        at += n * sizeof(T);
-        return v;
-    }
-};
-
 struct GraphData {
     int32_t n_kf, n_points;
     std::vector<int64_t> ids, slot_off, first, obs_off;
     std::vector<uint8_t> not_erase, slot_level, bad;
     std::vector<float> th_depth, slot_right, slot_depth;
     std::vector<int32_t> slot_point, found, visible, n_obs, obs_kf, obs_idx;
-    explicit GraphData(Reader &r) {
+    explicit GraphData(BlobReader &r) {
         n_kf = r.one<int32_t>(); n_points = r.one<int32_t>();
         const size_t K = (size_t)n_kf, P = (size_t)n_points;
         ids = r.many<int64_t>(K); not_erase = r.many<uint8_t>(K); th_depth = r.many<float>(K); slot_off = r.many<int64_t>(K + 1);
@@ -121,24 +98,20 @@ struct Graph {
     }
 };
 
-struct Writer {
-    std::vector<int32_t> all;
+struct CopyWriter : BlobWriter {
+    void word(int32_t x) { put(&x, 1); }
     void copy(const std::vector<int32_t> &w) {
-        all.push_back((int32_t)w.size());
-        all.insert(all.end(), w.begin(), w.end());
-    }
-    void save(const char *path) const {
-        FILE *f = std::fopen(path, "wb");
-        if (!f) throw std::runtime_error("cannot open output");
-        if (!all.empty() && std::fwrite(all.data(), 4, all.size(), f) != all.size()) throw std::runtime_error("short write");
-        std::fclose(f);
+        word((int32_t)w.size());
+        put(w);
     }
 };
 
-int run(const std::string &mode, const char *in, const char *out) {
-    Reader r(in);
+int run(int argc, char **argv) {
+    if (argc != 4) throw BlobUsage();
+    const std::string mode = argv[1];
+    BlobReader r(argv[2]);
     const GraphData d(r);
-    Writer W;
+    CopyWriter W;
     if (mode == "connections") {
         const int32_t n = r.one<int32_t>();
         const std::vector<int32_t> order = r.many<int32_t>((size_t)n);
@@ -156,7 +129,7 @@ int run(const std::string &mode, const char *in, const char *out) {
             std::vector<int32_t> w;
             g.dump(w);
             W.copy(w);
-            if (form) W.all.push_back((int32_t)(covis_host::calls() - before));
+            if (form) W.word((int32_t)(covis_host::calls() - before));
         }
     } else if (mode == "kfcull") {
         const int32_t mono = r.one<int32_t>(), n = r.one<int32_t>();
@@ -172,7 +145,7 @@ int run(const std::string &mode, const char *in, const char *out) {
             std::vector<int32_t> w;
             g.dump(w);
             W.copy(w);
-            if (form) W.all.push_back((int32_t)(covis_host::calls() - before));
+            if (form) W.word((int32_t)(covis_host::calls() - before));
         }
     } else if (mode == "mpcull") {
         const int32_t mono = r.one<int32_t>();
@@ -193,7 +166,7 @@ int run(const std::string &mode, const char *in, const char *out) {
             w.push_back((int32_t)recent.size());
             for (const MapPoint *p : recent) w.push_back(g.index(p));
             W.copy(w);
-            if (form) W.all.push_back((int32_t)(covis_host::calls() - before));
+            if (form) W.word((int32_t)(covis_host::calls() - before));
         }
     } else if (mode == "vote") {
         const int32_t n = r.one<int32_t>();
@@ -212,7 +185,7 @@ int run(const std::string &mode, const char *in, const char *out) {
             for (const auto &kw : counter) { w.push_back(g.index(kw.first)); w.push_back(kw.second); }
             for (const MapPoint *p : F.mvpMapPoints) w.push_back(g.index(p));
             W.copy(w);
-            if (form) W.all.push_back((int32_t)(covis_host::calls() - before));
+            if (form) W.word((int32_t)(covis_host::calls() - before));
         }
     } else if (mode == "walk") {
         const int32_t mono = r.one<int32_t>();
@@ -250,29 +223,14 @@ int run(const std::string &mode, const char *in, const char *out) {
             med.push_back(v[v.size() / 2]);
         }
         med.push_back((double)sink);                        // counter sizes, list lengths and local[0]'s bad flag over all runs
-        FILE *f = std::fopen(out, "wb");
-        if (!f || std::fwrite(med.data(), 8, med.size(), f) != med.size()) throw std::runtime_error("cannot write output");
-        std::fclose(f);
-        return 0;
+        W.put(med);
     } else {
-        std::fprintf(stderr, "unknown mode %s\n", mode.c_str());
-        return 2;
+        throw BlobUsage();
     }
-    W.save(out);
+    W.save(argv[3]);
     return 0;
 }
 
 }  // namespace
 
-int main(int argc, char **argv) {
-    if (argc != 4) {
-        std::fprintf(stderr, "usage: covis_adapter_prog connections|kfcull|mpcull|vote|walk IN OUT\n");
-        return 2;
-    }
-    try {
-        return run(argv[1], argv[2], argv[3]);
-    } catch (const std::exception &e) {
-        std::fprintf(stderr, "covis_adapter_prog: %s\n", e.what());
-        return 1;
-    }
-}
+int main(int argc, char **argv) { return blob_main(argc, argv, "covis_adapter_prog connections|kfcull|mpcull|vote|walk IN OUT", run); }

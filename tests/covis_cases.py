@@ -2,46 +2,15 @@
 yardstick), the host build of the kernels' arithmetic (tests/covis_prog.cpp) and the blobs both programs read.  A scene is built afresh
 for every run: the restatement mutates its graph."""
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import covis_restatement as R
+import host_prog
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sivo_amd", "csrc")
-API = os.path.join(ROOT, "sivo_amd", "api", "orbslam")
-TESTS = os.path.join(ROOT, "tests")
-SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
 LDS_KF = 8192                                                       # SIVO_COVIS_LDS_KF of include/sivo_hip.h
 SENTINEL = R.SENTINEL
-
-
-# ---- programs ------------------------------------------------------------------------------------------------------------------------
-def sanitizer_runtime_present(out_dir):
-    """Whether g++ can compile and link a trivial main with the sanitizer flags: decided before the programs under test are compiled."""
-    src, exe = out_dir / "san_probe.cpp", out_dir / "san_probe"
-    src.write_text("int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-std=c++14", *SANITIZE, str(src), "-o", str(exe)], capture_output=True, text=True, timeout=120)
-    return r.returncode == 0
-
-
-def build_prog(out_dir, name="covis_prog", sanitize=False):
-    exe = str(out_dir / (name + ("_san" if sanitize else "")))
-    flags = SANITIZE if sanitize else ["-O2"]
-    r = subprocess.run(["g++", "-std=c++14", *flags, "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", "-I" + API, "-I" + CSRC, "-I" + TESTS,
-                        os.path.join(TESTS, name + ".cpp"), "-o", exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
-def run_prog(exe, tmp_path, mode, blob):
-    fin, fout = tmp_path / (mode + ".in"), tmp_path / (mode + ".out")
-    fin.write_bytes(blob)
-    r = subprocess.run([exe, mode, str(fin), str(fout)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (mode, r.returncode, r.stderr[-3000:])
-    return fout.read_bytes()
+run_prog = host_prog.run                                            # (the tests' assertions call it by this name)
 
 
 # ---- blobs ---------------------------------------------------------------------------------------------------------------------------
@@ -83,13 +52,13 @@ def mpcull_blob(a, current, monocular):
 
 # ---- host build ----------------------------------------------------------------------------------------------------------------------
 def host_count(exe, tmp_path, t, sets, selfs):
-    raw = run_prog(exe, tmp_path, "count", count_blob(t, sets, selfs))
+    raw = host_prog.run(exe, tmp_path, "count", count_blob(t, sets, selfs))
     rc = int(np.frombuffer(raw, np.int32, 1)[0])
     return rc, np.frombuffer(raw, np.int32, len(sets) * t["n_kf"], 4).reshape(len(sets), t["n_kf"])
 
 
 def host_kfcull(exe, tmp_path, t, local, monocular):
-    raw = run_prog(exe, tmp_path, "kfcull", kfcull_blob(t, local, monocular))
+    raw = host_prog.run(exe, tmp_path, "kfcull", kfcull_blob(t, local, monocular))
     K, P = len(local), len(t["point_bad"])
     assert len(raw) == 4 + 9 * K + P
     return dict(rc=int(np.frombuffer(raw, np.int32, 1)[0]), n_mps=np.frombuffer(raw, np.int32, K, 4), n_redundant=np.frombuffer(raw, np.int32, K, 4 + 4 * K),
@@ -97,7 +66,7 @@ def host_kfcull(exe, tmp_path, t, local, monocular):
 
 
 def host_mpcull(exe, tmp_path, a, current, monocular):
-    raw = run_prog(exe, tmp_path, "mpcull", mpcull_blob(a, current, monocular))
+    raw = host_prog.run(exe, tmp_path, "mpcull", mpcull_blob(a, current, monocular))
     return int(np.frombuffer(raw, np.int32, 1)[0]), np.frombuffer(raw, np.uint8, len(a["found"]), 4)
 
 

@@ -12,18 +12,16 @@ Three groups of map points:
            mnMaxY (in view: the comparisons are strict), viewCos on either side of the limit, two visible points the caller skips.
 The expected values are the reference's own Frame::isInFrustum (oracle/_ref/libref_frame.so through pin_frame_common.reference_frame),
 recorded in tests/golden/frustum_reference.npz."""
+import functools
 import os
-import subprocess
 
 import numpy as np
 
+import host_prog
 import pin_frame_common as FC
 
 ROOT = FC.ROOT
 GOLDEN = os.path.join(ROOT, "tests", "golden", "frustum_reference.npz")
-CSRC = os.path.join(ROOT, "sivo_amd", "csrc")
-API = os.path.join(ROOT, "sivo_amd", "api")
-PROG = os.path.join(ROOT, "tests", "frustum_prog.cpp")
 ROWS, COLS = 352, 1024
 BOUNDS = (0.0, float(COLS), 0.0, float(ROWS))          # mnMinX, mnMaxX, mnMinY, mnMaxY without distortion (Frame.cc:436-440)
 SCALE_FACTOR, NLEVELS, COS_LIMIT = 1.2, 8, 0.5
@@ -253,33 +251,7 @@ def same_as_reference(group, got, want, what):
 # ---------------------------------------------------------------------------------------------------------------------
 # the host program
 # ---------------------------------------------------------------------------------------------------------------------
-SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-
-
-def sanitizer_runtime_present(out_dir):
-    """Whether g++ can compile and link a trivial main with the sanitizer flags: decided before the program under test is compiled, so
-    that only a missing runtime, never an error in that program, leads to the skip."""
-    src, exe = out_dir / "san_probe.cpp", out_dir / "san_probe"
-    src.write_text("int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-std=c++14", *SANITIZE, str(src), "-o", str(exe)], capture_output=True, text=True, timeout=120)
-    return r.returncode == 0
-
-
-def build_prog(out_dir, sanitize=False):
-    exe = str(out_dir / ("frustum_prog" + ("_san" if sanitize else "")))
-    flags = SANITIZE if sanitize else ["-O2"]
-    r = subprocess.run(["g++", "-std=c++14", *flags, "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", "-I" + API, "-I" + CSRC,
-                        "-I" + os.path.join(ROOT, "tests"), PROG, "-o", exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
-def run_prog(exe, tmp_path, mode, blob):
-    fin, fout = tmp_path / (mode + ".in"), tmp_path / (mode + ".out")
-    fin.write_bytes(blob)
-    r = subprocess.run([exe, mode, str(fin), str(fout)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (mode, r.returncode, r.stderr[-3000:])
-    return fout.read_bytes()
+run_prog = functools.partial(host_prog.run, timeout=120)              # (the tests' assertions call it by this name)
 
 
 def points_blob(g, n=None):

@@ -1,6 +1,7 @@
 // frustum_prog.cpp — the host build of the frustum cull (sivo_amd/csrc/frustum_math.hpp through tests/frustum_host_capi.hpp) and the C++
 // adapter over it (sivo_amd/api/orbslam/TrackingAdapter.h) with stand-in SLAM types; tests/test_pin_frustum.py compares what it writes
-// with the reference's Frame::isInFrustum.  No library, no device: the test also builds it with -fsanitize=address,undefined.
+// with the reference's Frame::isInFrustum.  No library, no device: the test builds it through tests/host_prog.py, plain and under the
+// sanitizers.
 //   prog cull IN OUT      IN: SivoFrustum, n (i64), pos (3n f32), normal (3n f32), min_dist, max_dist (n f32 each), skip (n bytes).
 //                         OUT: status (n bytes), proj_x, proj_y, proj_xr, view_cos (n f32 each), level (n i32), n_in_view (i32); the
 //                         outputs start from the sentinels -12345.f / -77, which the entries of a point out of view must keep.
@@ -16,17 +17,13 @@
 //                         OUT: the return value, nToMatch (i32 each), per point nVisible (i32), mnLastFrameSeen (i64), mbTrackInView
 //                         (i32), mTrackProjX, mTrackProjY, mTrackProjXR, mTrackViewCos (f32), mnTrackScaleLevel (i32); per key the point in
 //                         the slot (i32).
-#include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
+#include "blob_io.hpp"
 #include "orbslam/TrackingAdapter.h"
 #include "frustum_host_capi.hpp"
-
-template <class T>
-static bool rd(FILE *f, T *p, size_t n) { return n == 0 || fread(p, sizeof(T), n, f) == n; }
-template <class T>
-static void wr(FILE *f, const T *p, size_t n) { if (n) fwrite(p, sizeof(T), n, f); }
 
 static const float SENTINEL = -12345.f;
 
@@ -79,10 +76,11 @@ struct TFrame {
 struct Points {
     int64_t n = 0;
     std::vector<float> pos, normal, mind, maxd;
-    bool read(FILE *in) {
-        if (!rd(in, &n, 1) || n < 0 || n > (1 << 24)) return false;
-        pos.resize(3 * (size_t)n); normal.resize(3 * (size_t)n); mind.resize((size_t)n); maxd.resize((size_t)n);
-        return rd(in, pos.data(), pos.size()) && rd(in, normal.data(), normal.size()) && rd(in, mind.data(), mind.size()) && rd(in, maxd.data(), maxd.size());
+    bool read(BlobReader &in) {
+        n = in.one<int64_t>();
+        if (n < 0 || n > (1 << 24)) return false;
+        pos = in.many<float>(3 * (size_t)n); normal = in.many<float>(3 * (size_t)n); mind = in.many<float>((size_t)n); maxd = in.many<float>((size_t)n);
+        return true;
     }
     void fill(TMapPoint &p, size_t i) const {
         for (int k = 0; k < 3; ++k) { p.pos.at<float>(k, 0) = pos[3 * i + (size_t)k]; p.normal.at<float>(k, 0) = normal[3 * i + (size_t)k]; }
@@ -90,13 +88,13 @@ struct Points {
     }
 };
 
-static int cull(FILE *in, FILE *out, bool adapter) {
-    SivoFrustum f;
+static int cull(BlobReader &in, BlobWriter &out, bool adapter) {
+    const SivoFrustum f = in.one<SivoFrustum>();
     Points P;
-    if (!rd(in, &f, 1) || !P.read(in)) return 2;
+    if (!P.read(in)) return 2;
     const size_t n = (size_t)P.n;
-    std::vector<uint8_t> skip(n), status(n, 0);
-    if (!rd(in, skip.data(), n)) return 2;
+    const std::vector<uint8_t> skip = in.many<uint8_t>(n);
+    std::vector<uint8_t> status(n, 0);
     std::vector<float> px(n, SENTINEL), py(n, SENTINEL), pxr(n, SENTINEL), vc(n, SENTINEL);
     std::vector<int32_t> level(n, -77);
     if (!adapter) {
@@ -104,8 +102,8 @@ static int cull(FILE *in, FILE *out, bool adapter) {
         if (sivo_frustum_cull(&f, (int)n, P.pos.data(), P.normal.data(), P.mind.data(), P.maxd.data(), skip.data(), status.data(), px.data(), py.data(),
                               pxr.data(), vc.data(), level.data(), &count) != SIVO_OK)
             return 3;
-        wr(out, status.data(), n); wr(out, px.data(), n); wr(out, py.data(), n); wr(out, pxr.data(), n); wr(out, vc.data(), n); wr(out, level.data(), n);
-        wr(out, &count, 1);
+        out.put(status); out.put(px); out.put(py); out.put(pxr); out.put(vc); out.put(level);
+        out.put(&count, 1);
         return 0;
     }
     TFrame F;
@@ -120,51 +118,49 @@ static int cull(FILE *in, FILE *out, bool adapter) {
         status[i] = p.mbTrackInView;
         px[i] = p.mTrackProjX; py[i] = p.mTrackProjY; pxr[i] = p.mTrackProjXR; vc[i] = p.mTrackViewCos; level[i] = p.mnTrackScaleLevel;
     }
-    wr(out, status.data(), n); wr(out, px.data(), n); wr(out, py.data(), n); wr(out, pxr.data(), n); wr(out, vc.data(), n); wr(out, level.data(), n);
+    out.put(status); out.put(px); out.put(py); out.put(pxr); out.put(vc); out.put(level);
     return 0;
 }
 
-static int table(FILE *in, FILE *out) {
-    float lsf;
-    int32_t nlevels;
-    if (!rd(in, &lsf, 1) || !rd(in, &nlevels, 1) || nlevels < 1 || nlevels > 16 || !(lsf > 0.f)) return 2;
+static int table(BlobReader &in, BlobWriter &out) {
+    const float lsf = in.one<float>();
+    const int32_t nlevels = in.one<int32_t>();
+    if (nlevels < 1 || nlevels > 16 || !(lsf > 0.f)) return 2;
     float T[15] = {0};
     sivo::fr_level_table(lsf, nlevels, T);
-    wr(out, T, 15);
+    out.put(T, 15);
     for (int k = 0; k < nlevels - 1; ++k) {
         const int32_t lv[2] = {sivo::fr_level_direct(T[k], lsf, nlevels), sivo::fr_level_direct(nextafterf(T[k], INFINITY), lsf, nlevels)};
-        wr(out, lv, 2);
+        out.put(lv, 2);
     }
     return 0;
 }
 
-static int searchlocal(FILE *in, FILE *out) {
-    SivoFrustum f;
+static int searchlocal(BlobReader &in, BlobWriter &out) {
+    const SivoFrustum f = in.one<SivoFrustum>();
     float par[2];
-    int64_t id, nk;
-    if (!rd(in, &f, 1) || !rd(in, par, 2) || !rd(in, &id, 1) || !rd(in, &nk, 1) || nk < 0 || nk > (1 << 20)) return 2;
+    in.get(par, 2);
+    const int64_t id = in.one<int64_t>(), nk = in.one<int64_t>();
+    if (nk < 0 || nk > (1 << 20)) return 2;
     TFrame F;
     F.set(f, 1.2f);
     F.mnId = (long unsigned int)id;
-    std::vector<SivoKeyPoint> keys((size_t)nk);
-    std::vector<int32_t> slot((size_t)nk);
-    F.mvRight.resize((size_t)nk);
+    const std::vector<SivoKeyPoint> keys = in.many<SivoKeyPoint>((size_t)nk);
+    F.mvRight = in.many<float>((size_t)nk);
     F.mDescriptorsSemantic = cv::Mat::zeros((int)(nk > 0 ? nk : 1), 32, CV_8UC1);
-    if (!rd(in, keys.data(), keys.size()) || !rd(in, F.mvRight.data(), (size_t)nk) || !rd(in, F.mDescriptorsSemantic.data, 32 * (size_t)nk) ||
-        !rd(in, slot.data(), slot.size()))
-        return 2;
+    in.get(F.mDescriptorsSemantic.data, 32 * (size_t)nk);
+    const std::vector<int32_t> slot = in.many<int32_t>((size_t)nk);
     for (const SivoKeyPoint &k : keys) F.mvKeysSemantic.push_back(cv::KeyPoint(k.x, k.y, k.size, k.angle, k.response, k.octave, k.class_id));
     Points P;
     if (!P.read(in)) return 2;
     const size_t n = (size_t)P.n;
-    std::vector<uint8_t> bad(n), desc(32 * n);
-    std::vector<int64_t> seen(n);
-    std::vector<int32_t> obs(n);
-    int64_t m;
-    if (!rd(in, bad.data(), n) || !rd(in, seen.data(), n) || !rd(in, obs.data(), n) || !rd(in, desc.data(), desc.size()) || !rd(in, &m, 1) || m < 0 || m > (1 << 24))
-        return 2;
-    std::vector<int32_t> local((size_t)m);
-    if (!rd(in, local.data(), local.size())) return 2;
+    const std::vector<uint8_t> bad = in.many<uint8_t>(n);
+    const std::vector<int64_t> seen = in.many<int64_t>(n);
+    const std::vector<int32_t> obs = in.many<int32_t>(n);
+    const std::vector<uint8_t> desc = in.many<uint8_t>(32 * n);
+    const int64_t m = in.one<int64_t>();
+    if (m < 0 || m > (1 << 24)) return 2;
+    const std::vector<int32_t> local = in.many<int32_t>((size_t)m);
     std::vector<TMapPoint> pts(n);
     for (size_t i = 0; i < n; ++i) {
         P.fill(pts[i], i);
@@ -182,33 +178,31 @@ static int searchlocal(FILE *in, FILE *out) {
     }
     int32_t ret[2] = {0, -1};
     ret[0] = SIVO::SearchLocalPoints(F, vpLocal, par[0], par[1], &ret[1]);
-    wr(out, ret, 2);
+    out.put(ret, 2);
     for (const TMapPoint &p : pts) {
         const int32_t vis = p.nVisible, inview = p.mbTrackInView, lvl = p.mnTrackScaleLevel;
         const int64_t s = (int64_t)p.mnLastFrameSeen;
         const float t[4] = {p.mTrackProjX, p.mTrackProjY, p.mTrackProjXR, p.mTrackViewCos};
-        wr(out, &vis, 1); wr(out, &s, 1); wr(out, &inview, 1); wr(out, t, 4); wr(out, &lvl, 1);
+        out.put(&vis, 1); out.put(&s, 1); out.put(&inview, 1); out.put(t, 4); out.put(&lvl, 1);
     }
     for (TMapPoint *p : F.mvpMapPoints) {
         const int32_t s = p ? (int32_t)(p - pts.data()) : -1;
-        wr(out, &s, 1);
+        out.put(&s, 1);
     }
     SIVO::ORBmatcher::ReleaseDeviceFrames();
     return 0;
 }
 
-int main(int argc, char **argv) {
-    if (argc != 4) return 1;
-    FILE *in = fopen(argv[2], "rb"), *out = fopen(argv[3], "wb");
-    if (!in || !out) return 1;
-    int rc = 1;
-    try {
-        rc = !strcmp(argv[1], "cull") ? cull(in, out, false) : !strcmp(argv[1], "isinfrustum") ? cull(in, out, true)
-             : !strcmp(argv[1], "table") ? table(in, out) : !strcmp(argv[1], "searchlocal") ? searchlocal(in, out) : 1;
-    } catch (const std::exception &e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        rc = 5;
-    }
-    fclose(in);
-    return fclose(out) ? 1 : rc;
+// exit codes beside blob_main's: 2 a count out of range, 3 the cull's return code, 4 isInFrustum and mbTrackInView disagree
+static int run(int argc, char **argv) {
+    if (argc != 4) throw BlobUsage();
+    const std::string mode = argv[1];
+    BlobReader in(argv[2]);
+    BlobWriter out;
+    const int rc = mode == "cull" ? cull(in, out, false) : mode == "isinfrustum" ? cull(in, out, true) : mode == "table" ? table(in, out)
+                   : mode == "searchlocal" ? searchlocal(in, out) : throw BlobUsage();
+    out.save(argv[3]);
+    return rc;
 }
+
+int main(int argc, char **argv) { return blob_main(argc, argv, "frustum_prog cull|isinfrustum|table|searchlocal IN OUT", run); }

@@ -25,20 +25,16 @@
 //   prog refresh IN OUT       (device) IN as `local_mapping_prog refresh` reads it, then one byte per observation (1: its keyframe is bad).
 //                             A point's reference keyframe is the observation whose camera centre equals the record's ref_ow.
 //                             OUT per point: max, min, normal[3] (f32), descriptor (32 bytes).
-#include <cstdio>
 #include <cstring>
 #include <list>
+#include <string>
 #include <vector>
 
+#include "blob_io.hpp"
 #include "local_mapping_standins.hpp"
 #ifdef SIVO_LM_ON_HOST
 #include "local_mapping_host_capi.hpp"
 #endif
-
-template <class T>
-static bool rd(FILE *f, T *p, size_t n) { return n == 0 || fread(p, sizeof(T), n, f) == n; }
-template <class T>
-static void wr(FILE *f, const T *p, size_t n) { if (n) fwrite(p, sizeof(T), n, f); }
 
 static void key_descriptor(unsigned char *d, int frame, size_t i) {
     for (int b = 0; b < 32; ++b) d[b] = (unsigned char)((i * 37 + (size_t)b * 11 + (size_t)frame * 101 + ((i >> 3) * 7)) & 255);
@@ -50,11 +46,12 @@ struct Scene {
     float rf[2];
     double cov[36], th[2];
     int64_t n = 0;
-    bool read(FILE *in) {
+    bool read(BlobReader &in) {
         SivoTriKeyFrame k[2];
-        if (!rd(in, k, 2) || !rd(in, rf, 2) || !rd(in, cov, 36) || !rd(in, th, 2) || !rd(in, &n, 1) || n < 0) return false;
-        std::vector<SivoTriMatch> m((size_t)n);
-        if (!rd(in, m.data(), (size_t)n)) return false;
+        in.get(k, 2); in.get(rf, 2); in.get(cov, 36); in.get(th, 2);
+        n = in.one<int64_t>();
+        if (n < 0) return false;
+        const std::vector<SivoTriMatch> m = in.many<SivoTriMatch>((size_t)n);
         for (int f = 0; f < 2; ++f) {
             LKeyFrame &K = kf[f];
             K.set(k[f]);
@@ -84,7 +81,7 @@ struct Scene {
     }
 };
 
-static int gather(FILE *in, FILE *out) {
+static int gather(BlobReader &in, BlobWriter &out) {
     Scene s;
     if (!s.read(in)) return 2;
     SivoTriProblem P;
@@ -93,16 +90,16 @@ static int gather(FILE *in, FILE *out) {
     const float rf[2] = {P.ratio_factor, 0.f};
     const double th[2] = {P.th_confidence, P.th_entropy};
     const int64_t n = P.n;
-    wr(out, &P.kf1, 1); wr(out, &P.kf2, 1); wr(out, rf, 2); wr(out, P.state_cov, 36); wr(out, th, 2); wr(out, &n, 1); wr(out, m.data(), m.size());
+    out.put(&P.kf1, 1); out.put(&P.kf2, 1); out.put(rf, 2); out.put(P.state_cov, 36); out.put(th, 2); out.put(&n, 1); out.put(m);
     return 0;
 }
 
-static void write_point(FILE *out, const LMapPoint &p) {
+static void write_point(BlobWriter &out, const LMapPoint &p) {
     const float g[5] = {p.maxDistance, p.minDistance, p.normal.at<float>(0), p.normal.at<float>(1), p.normal.at<float>(2)};
-    wr(out, g, 5); wr(out, p.desc.data, 32);
+    out.put(g, 5); out.put(p.desc.data, 32);
 }
 
-static int triangulate(FILE *in, FILE *out) {
+static int triangulate(BlobReader &in, BlobWriter &out) {
     Scene s;
     if (!s.read(in)) return 2;
     LMap map;
@@ -110,17 +107,17 @@ static int triangulate(FILE *in, FILE *out) {
     const int nnew = SIVO::TriangulateMatches(&s.kf[0], &s.kf[1], s.pairs, &map, recent);
     if ((size_t)nnew != map.points.size() || recent.size() != map.points.size()) return 4;
     const int64_t count = nnew;
-    wr(out, &count, 1);
+    out.put(&count, 1);
     auto it = recent.begin();
     for (LMapPoint *p : map.points) {
         if (*it++ != p || p->ref != &s.kf[0] || p->observations.size() != 2) return 4;
         const int64_t idx[2] = {(int64_t)p->observations[&s.kf[0]], (int64_t)p->observations[&s.kf[1]]};
         if (s.kf[0].mvpMapPoints[(size_t)idx[0]] != p || s.kf[1].mvpMapPoints[(size_t)idx[1]] != p) return 4;
-        wr(out, idx, 2); wr(out, p->pos.ptr<float>(), 3); write_point(out, *p);
+        out.put(idx, 2); out.put(p->pos.ptr<float>(), 3); write_point(out, *p);
     }
     std::vector<uint8_t> slots((size_t)s.n);
     for (size_t i = 0; i < slots.size(); ++i) slots[i] = s.kf[0].mvpMapPoints[i] != nullptr;
-    wr(out, slots.data(), slots.size());
+    out.put(slots);
     for (LMapPoint *p : map.points) delete p;
     return 0;
 }
@@ -132,23 +129,24 @@ struct MapScene {
     std::vector<LKeyFrame> kf;          // [0] the current keyframe; one array: the observation maps walk it before the neighbours
     std::vector<LKeyFrame *> neigh;
     int64_t checks = 0;
-    bool read(FILE *in) {
-        int64_t nk;
+    bool read(BlobReader &in) {
+        const int64_t nk = in.one<int64_t>();
+        checks = in.one<int64_t>();
         double cov[36], th[2];
-        if (!rd(in, &nk, 1) || !rd(in, &checks, 1) || !rd(in, cov, 36) || !rd(in, th, 2) || nk < 0) return false;
+        in.get(cov, 36); in.get(th, 2);
+        if (nk < 0) return false;
         kf.resize((size_t)nk + 1);
         for (LKeyFrame &K : kf) {
-            SivoTriKeyFrame k;
-            int64_t n;
-            if (!rd(in, &k, 1) || !rd(in, &n, 1) || n < 0) return false;
-            std::vector<KeyRec> keys((size_t)n);
-            if (!rd(in, keys.data(), keys.size())) return false;
+            const SivoTriKeyFrame k = in.one<SivoTriKeyFrame>();
+            const int64_t n = in.one<int64_t>();
+            if (n < 0) return false;
+            const std::vector<KeyRec> keys = in.many<KeyRec>((size_t)n);
             K.set(k);
             K.mfScaleFactor = 1.2f;
             K.numSemanticKeys = (int)n;
             K.mvpMapPoints.assign((size_t)n, nullptr);
             K.mDescriptorsSemantic = cv::Mat::zeros((int)(n > 0 ? n : 1), 32, CV_8UC1);
-            if (!rd(in, K.mDescriptorsSemantic.data, 32 * (size_t)n)) return false;
+            in.get(K.mDescriptorsSemantic.data, 32 * (size_t)n);
             for (const KeyRec &q : keys) {
                 const size_t i = K.mvKeysSemantic.size();
                 K.mvKeysSemantic.push_back(cv::KeyPoint(q.x, q.y, 31.f, 0, 0, q.octave));
@@ -165,7 +163,7 @@ struct MapScene {
     }
 };
 
-static int walk(FILE *in, FILE *out) {
+static int walk(BlobReader &in, BlobWriter &out) {
     MapScene s;
     if (!s.read(in)) return 2;
     LKeyFrame *cur = &s.kf[0];
@@ -177,35 +175,33 @@ static int walk(FILE *in, FILE *out) {
             const int64_t k = pKF2 - &s.kf[1];
             for (size_t i = 0; i < cur->mvpMapPoints.size() && i < pKF2->mvpMapPoints.size(); ++i)
                 if (!cur->mvpMapPoints[i] && !pKF2->mvpMapPoints[i] && i % (size_t)(k + 2) == 0) pairs.push_back(std::make_pair(i, i));
-            wr(out, &k, 1);
-            for (int r = 0; r < 3; ++r) wr(out, F12.ptr<float>(r), 3);
+            out.put(&k, 1);
+            for (int r = 0; r < 3; ++r) out.put(F12.ptr<float>(r), 3);
         },
         [&](LKeyFrame *pKF2, const std::vector<std::pair<size_t, size_t> > &pairs) {
             const int64_t np = (int64_t)pairs.size();
-            wr(out, &np, 1);
+            out.put(&np, 1);
             int64_t nnew = 0;
             for (const auto &pr : pairs) {
                 const int64_t ij[2] = {(int64_t)pr.first, (int64_t)pr.second};
-                wr(out, ij, 2);
+                out.put(ij, 2);
                 if (pr.first % 3) continue;
                 made.push_back(new LMapPoint(cv::Mat::zeros(3, 1, CV_32F), cur, nullptr));
                 cur->AddMapPoint(made.back(), pr.first); pKF2->AddMapPoint(made.back(), pr.second);
                 ++nnew;
             }
-            wr(out, &nnew, 1);
+            out.put(&nnew, 1);
             return (int)nnew;
         });
     for (LMapPoint *p : made) delete p;
     return 0;
 }
 
-static int pinwalk(FILE *in, FILE *out) {
+static int pinwalk(BlobReader &in, BlobWriter &out) {
     MapScene s;
     if (!s.read(in)) return 2;
-    int64_t monocular;
-    if (!rd(in, &monocular, 1)) return 2;
-    for (LKeyFrame *k : s.neigh)
-        if (!rd(in, &k->medianDepth, 1)) return 2;
+    const int64_t monocular = in.one<int64_t>();
+    for (LKeyFrame *k : s.neigh) in.get(&k->medianDepth, 1);
     LKeyFrame *cur = &s.kf[0];
     const size_t n = cur->mvpMapPoints.size();
     LMap map;
@@ -219,18 +215,18 @@ static int pinwalk(FILE *in, FILE *out) {
             for (size_t i = 0; i < n; ++i)
                 if (!cur->mvpMapPoints[i] && !pKF2->mvpMapPoints[n - 1 - i] && i % (size_t)(k + 2) == 1) pairs.push_back(std::make_pair(i, n - 1 - i));
             if (++searched == s.checks) arrived = true;
-            wr(out, &k, 1);
-            for (int r = 0; r < 3; ++r) wr(out, F12.ptr<float>(r), 3);
+            out.put(&k, 1);
+            for (int r = 0; r < 3; ++r) out.put(F12.ptr<float>(r), 3);
             std::vector<uint8_t> occupied(n);
             for (size_t i = 0; i < n; ++i) occupied[i] = cur->mvpMapPoints[i] != nullptr;
-            wr(out, occupied.data(), n);
+            out.put(occupied.data(), n);
         },
         [&](LKeyFrame *pKF2, const std::vector<std::pair<size_t, size_t> > &pairs) {
             const int64_t np = (int64_t)pairs.size();
-            wr(out, &np, 1);
+            out.put(&np, 1);
             for (const auto &pr : pairs) {
                 const int64_t ij[2] = {(int64_t)pr.first, (int64_t)pr.second};
-                wr(out, ij, 2);
+                out.put(ij, 2);
             }
             const int nnew = SIVO::TriangulateMatches(cur, pKF2, pairs, &map, recent);
             std::vector<int64_t> made;
@@ -243,14 +239,14 @@ static int pinwalk(FILE *in, FILE *out) {
             }
             const int64_t count = (int64_t)(made.size() / 2);
             if (count != nnew) throw std::logic_error("pinwalk: the slots and TriangulateMatches' count disagree");
-            wr(out, &count, 1); wr(out, made.data(), made.size()); wr(out, pos.data(), pos.size());
+            out.put(&count, 1); out.put(made.data(), made.size()); out.put(pos.data(), pos.size());
             return nnew;
         });
     for (LMapPoint *p : map.points) delete p;
     return 0;
 }
 
-static int create(FILE *in, FILE *out) {
+static int create(BlobReader &in, BlobWriter &out) {
     MapScene s;
     if (!s.read(in)) return 2;
     LMap map;
@@ -258,28 +254,27 @@ static int create(FILE *in, FILE *out) {
     int64_t calls = 0;
     const int64_t nnew = SIVO::CreateNewMapPoints(&s.kf[0], s.neigh, &map, false, recent, [&] { return ++calls > s.checks; });
     if ((size_t)nnew != map.points.size() || recent.size() != map.points.size()) return 4;
-    wr(out, &nnew, 1);
+    out.put(&nnew, 1);
     for (LMapPoint *p : map.points) {
         if (p->ref != &s.kf[0] || p->observations.size() != 2) return 4;
         auto other = p->observations.begin();
         if (other->first == &s.kf[0]) ++other;
         const int64_t rec[3] = {(int64_t)(other->first - &s.kf[1]), (int64_t)p->observations[&s.kf[0]], (int64_t)other->second};
         if (s.kf[0].mvpMapPoints[(size_t)rec[1]] != p || other->first->mvpMapPoints[(size_t)rec[2]] != p) return 4;
-        wr(out, rec, 3); wr(out, p->pos.ptr<float>(), 3); write_point(out, *p);
+        out.put(rec, 3); out.put(p->pos.ptr<float>(), 3); write_point(out, *p);
     }
     for (LMapPoint *p : map.points) delete p;
     return 0;
 }
 
-static int refresh(FILE *in, FILE *out) {
-    int64_t np;
-    if (!rd(in, &np, 1) || np < 0) return 2;
-    std::vector<int64_t> doff((size_t)np + 1), ooff((size_t)np + 1);
-    if (!rd(in, doff.data(), doff.size()) || !rd(in, ooff.data(), ooff.size())) return 2;
+static int refresh(BlobReader &in, BlobWriter &out) {
+    const int64_t np = in.one<int64_t>();
+    if (np < 0) return 2;
+    const std::vector<int64_t> doff = in.many<int64_t>((size_t)np + 1), ooff = in.many<int64_t>((size_t)np + 1);
     const size_t nd = (size_t)doff[np], no = (size_t)ooff[np];
-    std::vector<uint8_t> desc(32 * nd), bad(no);
-    std::vector<float> ow(3 * no), pt(8 * (size_t)np);
-    if (!rd(in, desc.data(), desc.size()) || !rd(in, ow.data(), ow.size()) || !rd(in, pt.data(), pt.size()) || !rd(in, bad.data(), no)) return 2;
+    const std::vector<uint8_t> desc = in.many<uint8_t>(32 * nd);
+    const std::vector<float> ow = in.many<float>(3 * no), pt = in.many<float>(8 * (size_t)np);
+    const std::vector<uint8_t> bad = in.many<uint8_t>(no);
     std::vector<LKeyFrame> kfs(no);                 // one keyframe per observation, in observation order (the map walks them by address)
     std::vector<LMapPoint *> points;
     size_t d = 0;
@@ -316,19 +311,18 @@ static int refresh(FILE *in, FILE *out) {
     return 0;
 }
 
+// exit codes beside blob_main's: 2 a count out of range, 3 a scene that contradicts itself, 4 what the adapter left contradicts its count
+static int run(int argc, char **argv) {
+    if (argc != 4) throw BlobUsage();
+    const std::string mode = argv[1];
+    BlobReader in(argv[2]);
+    BlobWriter out;
+    const int rc = mode == "gather" ? gather(in, out) : mode == "triangulate" ? triangulate(in, out) : mode == "refresh" ? refresh(in, out)
+                   : mode == "walk" ? walk(in, out) : mode == "create" ? create(in, out) : mode == "pinwalk" ? pinwalk(in, out) : throw BlobUsage();
+    out.save(argv[3]);
+    return rc;
+}
+
 int main(int argc, char **argv) {
-    if (argc != 4) return 1;
-    FILE *in = fopen(argv[2], "rb"), *out = fopen(argv[3], "wb");
-    if (!in || !out) return 1;
-    int rc = 1;
-    try {
-        rc = !strcmp(argv[1], "gather") ? gather(in, out) : !strcmp(argv[1], "triangulate") ? triangulate(in, out)
-             : !strcmp(argv[1], "refresh") ? refresh(in, out) : !strcmp(argv[1], "walk") ? walk(in, out)
-             : !strcmp(argv[1], "create") ? create(in, out) : !strcmp(argv[1], "pinwalk") ? pinwalk(in, out) : 1;
-    } catch (const std::exception &e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        rc = 5;
-    }
-    fclose(in);
-    return fclose(out) ? 1 : rc;
+    return blob_main(argc, argv, "local_mapping_adapter_prog gather|triangulate|refresh|walk|create|pinwalk IN OUT", run);
 }

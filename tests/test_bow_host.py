@@ -11,31 +11,19 @@ import numpy as np
 import pytest
 
 import bow_restatement as BR
+import host_prog
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sivo_amd", "csrc")
+ROOT = host_prog.ROOT
 API = os.path.join(ROOT, "sivo_amd", "api")
-PROG = os.path.join(ROOT, "tests", "bow_prog.cpp")
 NAMES = ("sivo_voc_create_from_text", "sivo_voc_create", "sivo_voc_info", "sivo_voc_destroy", "sivo_bow_transform", "sivo_bow_transform_batch",
          "sivo_bowdb_create", "sivo_bowdb_add", "sivo_bowdb_erase", "sivo_bowdb_clear", "sivo_bowdb_destroy",
          "sivo_bowdb_size", "sivo_bowdb_query")
 
 
-def build_prog(tmp_path, extra=()):
-    exe = str(tmp_path / ("bow_prog" + ("_san" if extra else "")))
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", *extra, "-I" + CSRC, PROG, "-o", exe],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 def run_transform(exe, tmp_path, voc_path, sets, levelsup):
-    fin, fout = tmp_path / "t.in", tmp_path / "t.out"
-    fin.write_bytes(np.array([len(sets), levelsup], np.int64).tobytes()
-                    + b"".join(np.array([len(s)], np.int64).tobytes() + np.ascontiguousarray(s, np.uint8).tobytes() for s in sets))
-    r = subprocess.run([exe, "transform", str(voc_path), str(fin), str(fout)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
-    raw, at, out = fout.read_bytes(), 0, []
+    blob = (np.array([len(sets), levelsup], np.int64).tobytes()
+            + b"".join(np.array([len(s)], np.int64).tobytes() + np.ascontiguousarray(s, np.uint8).tobytes() for s in sets))
+    raw, at, out = host_prog.run(exe, tmp_path, "transform", blob, extra_args=(voc_path,), timeout=120), 0, []
     for _ in sets:
         n, nw, nf, m = np.frombuffer(raw, np.int64, 4, at)
         at += 32
@@ -51,11 +39,8 @@ def run_transform(exe, tmp_path, voc_path, sets, levelsup):
 
 def run_query(exe, tmp_path, stored, q):
     vec = lambda w, v: np.array([len(w)], np.int64).tobytes() + np.asarray(w, np.int32).tobytes() + np.asarray(v, np.float64).tobytes()
-    fin, fout = tmp_path / "q.in", tmp_path / "q.out"
-    fin.write_bytes(np.array([len(stored)], np.int64).tobytes() + b"".join(vec(*e) for e in stored) + vec(*q))
-    r = subprocess.run([exe, "query", str(fin), str(fout)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
-    rec = np.frombuffer(fout.read_bytes(), np.dtype([("common", np.int32), ("first_word", np.int32), ("score", np.float64)]))
+    raw = host_prog.run(exe, tmp_path, "query", np.array([len(stored)], np.int64).tobytes() + b"".join(vec(*e) for e in stored) + vec(*q), timeout=120)
+    rec = np.frombuffer(raw, np.dtype([("common", np.int32), ("first_word", np.int32), ("score", np.float64)]))
     return {k: rec[k] for k in ("common", "first_word", "score")}
 
 
@@ -107,7 +92,7 @@ def check_host(exe, tmp_path):
 
 
 def test_host_build_of_the_arithmetic_and_the_loader_equals_the_restatement(tmp_path):
-    self_score = check_host(build_prog(tmp_path), tmp_path)
+    self_score = check_host(host_prog.build("bow_prog", tmp_path), tmp_path)
     print("score of a vector against itself:", repr(float(self_score)))
 
 
@@ -153,12 +138,14 @@ def check_loader_rejects(exe, tmp_path):
 
 
 def test_loader_rejects_malformed_files(tmp_path):
-    check_loader_rejects(build_prog(tmp_path), tmp_path)
+    check_loader_rejects(host_prog.build("bow_prog", tmp_path), tmp_path)
 
 
 def test_host_build_under_address_and_undefined_sanitizers(tmp_path):
     """The stand-alone program built with -fsanitize=address,undefined and run directly, on the well-formed and the malformed files."""
-    exe = build_prog(tmp_path, ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    if not host_prog.sanitizer_runtime_present(tmp_path):
+        pytest.skip("the sanitizer runtime (libasan / libubsan) is not installed: a trivial main does not link with -fsanitize")
+    exe = host_prog.build("bow_prog", tmp_path, sanitize=True)
     check_host(exe, tmp_path)
     check_loader_rejects(exe, tmp_path)
 
@@ -281,25 +268,6 @@ def test_headers_compile_against_the_real_type_names(tmp_path, header):
     assert r.returncode == 0, r.stderr[-3000:]
 
 
-SCORE_PROG = r'''#include <cstdio>
-#include "orbslam/ORBVocabulary.h"
-int main(int argc, char **argv) {                     // pairs of vectors: n, n x (word value-as-hex-float), twice per line group
-    SIVO::ORBVocabulary voc;
-    std::FILE *f = std::fopen(argv[argc - 1], "r");
-    int n;
-    while (f && std::fscanf(f, "%d", &n) == 1) {
-        DBoW2::BowVector v[2];
-        for (int k = 0; k < 2; ++k) {
-            if (k && std::fscanf(f, "%d", &n) != 1) return 1;
-            for (int i = 0; i < n; ++i) { unsigned w; double x; if (std::fscanf(f, "%u %la", &w, &x) != 2) return 1; v[k][w] = x; }
-        }
-        std::printf("%a\n", voc.score(v[0], v[1]));
-    }
-    return voc.empty() && voc.size() == 0 ? 0 : 1;
-}
-'''
-
-
 def test_orbvocabulary_score_on_the_host_equals_the_restatement(tmp_path):
     """ORBVocabulary::score needs no device: the ordered L1 arithmetic over two std::maps, bit for bit."""
     rng = np.random.default_rng(12)
@@ -307,11 +275,7 @@ def test_orbvocabulary_score_on_the_host_equals_the_restatement(tmp_path):
     pairs = [(q, BR.random_vector(rng, 400, int(n))) for n in (1, 50, 120, 399)] + [(q, q), (q, (np.zeros(0, np.int32), np.zeros(0)))]
     fin = tmp_path / "pairs.txt"
     fin.write_text("\n".join(" ".join([str(len(w))] + [f"{int(a)} {float(b).hex()}" for a, b in zip(w, v)]) for p in pairs for w, v in p) + "\n")
-    tu, exe, lib = tmp_path / "score.cpp", str(tmp_path / "score"), os.path.join(ROOT, "sivo_amd")
-    tu.write_text(SCORE_PROG)
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-ffp-contract=off", "-I" + API, str(tu), "-o", exe, "-L" + lib, "-lsivo_hip", "-Wl,-rpath," + lib],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = host_prog.build("bow_score_prog", tmp_path, link_lib=True)
     r = subprocess.run([exe, str(fin)], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     got = np.array([float.fromhex(x) for x in r.stdout.split()])

@@ -12,18 +12,19 @@ import pytest
 import covis_adapter_cases as A
 import covis_cases as P
 import covis_restatement as R
+import host_prog
 
-ROOT = P.ROOT
+ROOT = host_prog.ROOT
 
 
 @pytest.fixture(scope="module")
 def prog(tmp_path_factory):
-    return P.build_prog(tmp_path_factory.mktemp("covis_prog"))
+    return host_prog.build("covis_prog", tmp_path_factory.mktemp("covis_prog"))
 
 
 @pytest.fixture(scope="module")
 def adapter_prog(tmp_path_factory):
-    return P.build_prog(tmp_path_factory.mktemp("covis_adapter_prog"), "covis_adapter_prog")
+    return host_prog.build("covis_adapter_prog", tmp_path_factory.mktemp("covis_adapter_prog"))
 
 
 # ---- counts ------------------------------------------------------------------------------------------------------------------------
@@ -251,17 +252,8 @@ def test_header_declares_and_library_exports_the_entry_points():
 
 
 def test_ctypes_table_matches_the_header(tmp_path):
-    import subprocess
     from sivo_amd import covisibility
-    t = covisibility._Table
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sivo_hip.h"\nint main(void) {\n  printf(" %zu", sizeof(SivoObsTable));\n'
-                   + "".join('  printf(" %%zu", offsetof(SivoObsTable, %s));\n' % f[0] for f in t._fields_) + "  return 0;\n}\n")
-    exe = str(tmp_path / "sz")
-    r = subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split()]
-    assert got == [C.sizeof(t)] + [getattr(t, f[0]).offset for f in t._fields_]
+    host_prog.c_layout(tmp_path, "SivoObsTable", covisibility._Table)
 
 
 def invalid_calls(cov):
@@ -388,9 +380,9 @@ def test_sanitizer_builds_of_both_programs_agree(prog, adapter_prog, tmp_path, t
     """Both stand-alone programs built a second time with -fsanitize=address,undefined and run directly (each has its own main: nothing
     is preloaded) on a cut of the scenes: the same bytes as the plain build, and no report."""
     san_dir = tmp_path_factory.mktemp("covis_prog_san")
-    if not P.sanitizer_runtime_present(san_dir):
+    if not host_prog.sanitizer_runtime_present(san_dir):
         pytest.skip("the sanitizer runtime (libasan / libubsan) is not installed: a trivial main does not link with -fsanitize")
-    san = P.build_prog(san_dir, sanitize=True)
+    san = host_prog.build("covis_prog", san_dir, sanitize=True)
     for name in ("n_kf_1", "n_kf_65", "lds_bound_%d" % (P.LDS_KF + 1), "set_sizes", "one_counter"):
         t, sets, selfs, _ = P.count_arrays(name)
         blob = P.count_blob(t, sets, selfs)
@@ -402,7 +394,7 @@ def test_sanitizer_builds_of_both_programs_agree(prog, adapter_prog, tmp_path, t
     for n, mono in P.MP_RUNS:
         blob = P.mpcull_blob(R.export_recent(P.mp_objects(n)), P.MP_CURRENT, mono)
         assert P.run_prog(prog, tmp_path, "mpcull", blob) == P.run_prog(san, tmp_path, "mpcull", blob)
-    asan = P.build_prog(san_dir, "covis_adapter_prog", sanitize=True)
+    asan = host_prog.build("covis_adapter_prog", san_dir, sanitize=True)
     for mode, blob in A.all_blobs():
         assert P.run_prog(adapter_prog, tmp_path, mode, blob) == P.run_prog(asan, tmp_path, mode, blob), mode
     walk = [np.frombuffer(P.run_prog(e, tmp_path, "walk", A.walk_blob(2)), np.float64) for e in (adapter_prog, asan)]

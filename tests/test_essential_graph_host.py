@@ -12,21 +12,10 @@ import pytest
 
 from conftest import ROOT
 import essential_graph_restatement as E
+import host_prog
 
 API = os.path.join(ROOT, "sivo_amd", "api")
 PROG = os.path.join(ROOT, "tests", "essential_graph_prog.cpp")
-
-
-def build_prog(tmp_path, device):
-    exe = str(tmp_path / ("eg_prog_dev" if device else "eg_prog"))
-    cmd = ["g++", "-std=c++14", "-O2", "-Wall", "-I" + API, PROG, "-o", exe]
-    if device:
-        lib = os.path.join(ROOT, "sivo_amd")
-        cmd[4:4] = ["-DSIVO_ESSENTIAL_GRAPH_ON_DEVICE"]
-        cmd += ["-L" + lib, "-lsivo_hip", "-Wl,-rpath," + lib]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
 
 
 @pytest.mark.parametrize("sigma", [0.0, 0.3])
@@ -221,10 +210,8 @@ def _parse_gather(out):
 @pytest.mark.parametrize("n_kf,seed,fix_scale", [(30, 1, True), (150, 2, False)])
 def test_gather_matches_the_reference_walk(tmp_path, n_kf, seed, fix_scale):
     m = E.make_map(n_kf, seed, fix_scale=fix_scale, n_points=20)
-    exe = build_prog(tmp_path, False)
-    r = subprocess.run([exe, "gather"], input=E.map_text(m), capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    siw, fixed, vertex, ij, meas = _parse_gather(r.stdout)
+    exe = host_prog.build("essential_graph_prog", tmp_path)
+    siw, fixed, vertex, ij, meas = _parse_gather(host_prog.run_text(exe, ["gather"], E.map_text(m), 60))
     want_siw, want_fixed, want_vertex, e = E.gather(m)
     assert np.array_equal(vertex, want_vertex) and np.array_equal(fixed, want_fixed)
     assert siw.tobytes() == want_siw.tobytes()
@@ -249,10 +236,9 @@ def test_pose_write_back_is_bit_exact(tmp_path):
     m = E.make_map(12, 3, n_points=0)
     rng = np.random.default_rng(5)
     S = np.stack([E.exp(np.concatenate([rng.normal(size=3), rng.normal(size=3) * 4, [rng.normal() * 0.3]])) for _ in range(20)])
-    exe = build_prog(tmp_path, False)
+    exe = host_prog.build("essential_graph_prog", tmp_path)
     text = E.map_text(m) + "\n".join(" ".join(repr(float(v)) for v in s) for s in S) + "\n"
-    r = subprocess.run([exe, "pose"], input=text, capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    got = np.array([[float.fromhex(v) for v in ln.split()] for ln in r.stdout.strip().splitlines()], np.float32)
+    out = host_prog.run_text(exe, ["pose"], text, 60)
+    got = np.array([[float.fromhex(v) for v in ln.split()] for ln in out.strip().splitlines()], np.float32)
     want = np.stack([E.pose_from_sim3(s)[:3].reshape(12) for s in S])
     assert got.tobytes() == want.tobytes()

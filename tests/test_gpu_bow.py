@@ -2,16 +2,15 @@
 restatement (tests/bow_restatement.py) BIT FOR BIT: word and node ids, the CSR form, the values and the scores as doubles."""
 import copy
 import functools
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import bow_restatement as BR
+import host_prog
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -141,7 +140,6 @@ def test_erase_then_query_and_clear_then_add():
 # ---------------------------------------------------------------------------------------------------------------------
 # SIVO::ORBVocabulary / SIVO::KeyFrameDatabase over stand-in SLAM types
 # ---------------------------------------------------------------------------------------------------------------------
-ADAPTER_PROG = os.path.join(ROOT, "tests", "bow_adapter_prog.cpp")
 N_KF, LEVELSUP = 60, 1
 ADD, ERASE, LOOP, RELOC, CLEAR = range(5)
 
@@ -245,10 +243,7 @@ def run_adapter(tmp_path, v, kfs, connected, ordered, frames, ops):
     fvoc, fin, fout = tmp_path / "voc.txt", tmp_path / "scene.bin", tmp_path / "out.txt"
     fvoc.write_text(v.text())
     fin.write_bytes(b"".join(blob))
-    exe, lib = str(tmp_path / "bow_adapter_prog"), os.path.join(ROOT, "sivo_amd")
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-I" + os.path.join(lib, "api"), "-I" + os.path.join(ROOT, "tests"), ADAPTER_PROG, "-o", exe,
-                        "-L" + lib, "-lsivo_hip", "-Wl,-rpath," + lib], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = host_prog.build("bow_adapter_prog", tmp_path, link_lib=True)
     r = subprocess.run([exe, str(fvoc), str(fin), str(fout)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     got_q, got_k, got_b = {}, {}, {}

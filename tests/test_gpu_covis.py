@@ -6,6 +6,7 @@ import pytest
 
 import covis_cases as P
 import covis_restatement as R
+import host_prog
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +19,7 @@ def cov():
 
 @pytest.fixture(scope="module")
 def prog(tmp_path_factory):
-    return P.build_prog(tmp_path_factory.mktemp("covis_prog_gpu"))
+    return host_prog.build("covis_prog", tmp_path_factory.mktemp("covis_prog_gpu"))
 
 
 def table_of(cov, t):

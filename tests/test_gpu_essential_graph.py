@@ -2,13 +2,11 @@
 (tests/essential_graph_restatement.py): parity on synthetic maps for both scale settings, convergence to a known truth, a 2000-keyframe
 map (run-to-run bit identity, chi2 reduction, scipy.sparse parity), the edge cases, the point correction (bit-exact) and the C++ member
 over the stand-in map against the Python binding (bit-exact)."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import essential_graph_restatement as E
-from test_essential_graph_host import build_prog
+import host_prog
 
 pytestmark = pytest.mark.gpu
 
@@ -115,10 +113,8 @@ def test_point_correction_bit_exact():
 @pytest.mark.parametrize("fix_scale", [True, False])
 def test_cpp_member_matches_the_binding(tmp_path, fix_scale):
     m = E.make_map(120, 31, fix_scale=fix_scale, n_points=300)
-    exe = build_prog(tmp_path, True)
-    r = subprocess.run([exe, "run"], input=E.map_text(m), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = r.stdout.strip().splitlines()
+    exe = host_prog.build("essential_graph_prog", tmp_path, link_lib=True, defines=("SIVO_ESSENTIAL_GRAPH_ON_DEVICE",))
+    lines = host_prog.run_text(exe, ["run"], E.map_text(m), 300).strip().splitlines()
     nk = len(m["kfs"])
     poses = np.array([[float.fromhex(v) for v in ln.split()] for ln in lines[:nk]], np.float32)
     pts = np.array([[float.fromhex(v) for v in ln.split()] for ln in lines[nk:]], np.float32)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import frustum_pin_cases as P
+import host_prog
 import search_local_cases as S
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +14,7 @@ F32 = np.float32
 
 @pytest.fixture(scope="module")
 def prog(tmp_path_factory):
-    return P.build_prog(tmp_path_factory.mktemp("frustum_prog"))
+    return host_prog.build("frustum_prog", tmp_path_factory.mktemp("frustum_prog"))
 
 
 def frustum_of(group, nlevels=P.NLEVELS):

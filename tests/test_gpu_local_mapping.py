@@ -1,11 +1,11 @@
 """sivo_triangulate / sivo_triangulate_batch (sivo_amd/csrc/triangulate.hip) and sivo_mappoint_refresh (sivo_amd/csrc/mappoint.hip)
 against the numpy restatements (tests/triangulate_restatement.py, tests/mappoint_restatement.py) BIT FOR BIT."""
 import functools
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_prog
 import mappoint_restatement as MR
 import test_local_mapping_host as H
 import triangulate_restatement as TR
@@ -149,20 +149,11 @@ def key_descriptors(frame, n):
     return ((i * 37 + b * 11 + frame * 101 + (i >> 3) * 7) & 255).astype(np.uint8)
 
 
-def run_prog(tmp_path, mode, blob):
-    exe = H.build_adapter_prog(tmp_path)
-    fin, fout = tmp_path / "a.in", tmp_path / "a.out"
-    fin.write_bytes(blob)
-    r = subprocess.run([exe, mode, str(fin), str(fout)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    return fout.read_bytes()
-
-
 def test_cpp_triangulate_matches_equals_the_python_path(tmp_path):
     from sivo_amd import local_mapping as LM
     p = H.adapter_problem()
     m, n = p["matches"], len(p["matches"])
-    raw = run_prog(tmp_path, "triangulate", H.tri_blob(p))
+    raw = host_prog.run(H.adapter_prog(tmp_path), tmp_path, "triangulate", H.tri_blob(p), timeout=120)
     res = run(p)
     acc = np.flatnonzero(res["status"] == TR.ACCEPTED)
     k = len(acc)
@@ -195,7 +186,7 @@ def test_cpp_refresh_map_points_equals_the_python_path(tmp_path):
     rec = np.concatenate([s["pos"], s["ref_ow"], s["level_scale"][:, None], s["last_scale"][:, None]], axis=1).astype(np.float32)
     blob = b"".join([np.array([n], np.int64).tobytes(), s["desc_off"].astype(np.int64).tobytes(), s["obs_off"].astype(np.int64).tobytes(),
                      s["desc"].tobytes(), s["obs_ow"].tobytes(), rec.tobytes(), is_bad.tobytes()])
-    raw = run_prog(tmp_path, "refresh", blob)
+    raw = host_prog.run(H.adapter_prog(tmp_path), tmp_path, "refresh", blob, timeout=120)
     got = np.frombuffer(raw, np.dtype([("geom", np.float32, 5), ("desc", np.uint8, 32)]), n)
     ref = LM.refresh_map_points(**s)
     want_geom = np.concatenate([ref["max_dist"][:, None], ref["min_dist"][:, None], ref["normal"]], axis=1)
@@ -212,7 +203,7 @@ def test_cpp_create_new_map_points_equals_the_python_path(tmp_path):
     from sivo_amd import local_mapping as LM, matcher as M
     sc = H.map_scene()
     frames = sc["frames"]
-    raw = run_prog(tmp_path, "create", H.map_blob(sc, 5))
+    raw = host_prog.run(H.adapter_prog(tmp_path), tmp_path, "create", H.map_blob(sc, 5), timeout=120)
     k1, cur, d1 = frames[0]
     F = np.float32
 

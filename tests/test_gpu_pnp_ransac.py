@@ -3,12 +3,12 @@
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+import host_prog
 import pnp_ransac_restatement as R
 import test_pnp_ransac_host as H
 
@@ -155,10 +155,8 @@ def test_cpp_class_equals_python_class(tmp_path):
                                  randint=lambda lo, hi, it=it: lo + next(it) % (hi - lo + 1))
         s.set_ransac_parameters(par[0], par[1], par[2], 4, par[3], par[4])
         solvers.append(s)
-    exe = H.build_prog(tmp_path)
-    r = subprocess.run([exe, "run", str(max_calls)], input=text, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    lines = r.stdout.strip().splitlines()
+    exe = host_prog.build("pnp_ransac_prog", tmp_path, link_lib=True)
+    lines = host_prog.run_text(exe, ["run", max_calls], text, 120).strip().splitlines()
     pnp_solver.PnPsolver.solve_all(solvers + [None])
     done, calls, pos = [False] * 3, [0] * 3, 0
     accepted, no_more_seen = set(), set()

@@ -1,13 +1,11 @@
 """sivo_sim3_optimize / sivo_sim3_optimize_batch (sivo_amd/csrc/sim3.hip) against the float64 restatement of
 Optimizer::OptimizeSim3 (tests/sim3_restatement.py), and Optimizer::OptimizeSim3 over stand-in keyframes
 (-DSIVO_SIM3_ON_DEVICE) against the Python binding."""
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_prog
 import sim3_restatement as R
-from test_sim3_host import build_prog
 
 pytestmark = pytest.mark.gpu
 
@@ -95,10 +93,8 @@ def test_cpp_member_equals_python_binding(tmp_path, fix_scale):
     from sivo_amd import optimizer
     sc = R.make_scene(150, 707, scale=1.0 if fix_scale else 1.1, outliers=0.15, fix_scale=fix_scale)
     kf1, kf2, pts, m1 = R.keyframe_pair(sc, 708, random_pose=False, n_extra=20)
-    exe = build_prog(tmp_path, True)
-    r = subprocess.run([exe, "run"], input=R.scene_text(sc, kf1, kf2, pts, m1), capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    lines = r.stdout.strip().splitlines()
+    exe = host_prog.build("sim3_adapter_prog", tmp_path, link_lib=True, defines=("SIVO_SIM3_ON_DEVICE",))
+    lines = host_prog.run_text(exe, ["run"], R.scene_text(sc, kf1, kf2, pts, m1), 120).strip().splitlines()
     n_in = int(lines[0])
     s12 = np.array([float.fromhex(v) for v in lines[1].split()])
     kept = np.array([int(v) for v in lines[2].split()])

@@ -3,14 +3,13 @@
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+import host_prog
 import sim3_ransac_restatement as R
-from test_sim3_ransac_host import build_prog
 
 pytestmark = pytest.mark.gpu
 
@@ -138,7 +137,7 @@ def test_cpp_class_equals_python_class(tmp_path):
     C++ class (through tests/sim3_ransac_prog.cpp) and the Python class, given the same draws, return the same matrices (hex
     floats), inlier vectors and bNoMore at every call."""
     from sivo_amd import sim3_solver
-    exe = build_prog(tmp_path)
+    exe = host_prog.build("sim3_ransac_prog", tmp_path, link_lib=True)
     cands = [("word_65", True, (0.99, 20, 300)), ("outliers30", False, (0.99, 100, 40)), ("all_outliers", True, (0.99, 20, 23))]
     text, solvers, checkers = [str(len(cands))], [], []
     for k, (name, fix, par) in enumerate(cands):
@@ -151,9 +150,7 @@ def test_cpp_class_equals_python_class(tmp_path):
         s.set_ransac_parameters(*par)
         solvers.append(s)
         checkers.append(R.Sequential(len(idx), lambda h, s=s: (int(s.result["count"][h]), h), *par))
-    r = subprocess.run([exe, "run"], input="\n".join(text) + "\n", capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    lines = r.stdout.strip().splitlines()
+    lines = host_prog.run_text(exe, ["run"], "\n".join(text) + "\n", 120).strip().splitlines()
     sim3_solver.Sim3Solver.solve_all(solvers + [None])
     discarded, pos, accepted = [False] * len(cands), 0, 0
     while not all(discarded):

@@ -8,37 +8,24 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_prog
 import mappoint_restatement as MR
 import triangulate_restatement as TR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sivo_amd", "csrc")
+ROOT = host_prog.ROOT
 API = os.path.join(ROOT, "sivo_amd", "api")
-PROG = os.path.join(ROOT, "tests", "local_mapping_prog.cpp")
 F, D = np.float32, np.float64
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the kernels' arithmetic, compiled for the host
 # ---------------------------------------------------------------------------------------------------------------------
-def build_prog(tmp_path, extra=()):
-    exe = str(tmp_path / ("local_mapping_prog" + ("_san" if extra else "")))
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", *extra, "-I" + CSRC, PROG, "-o", exe],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 def run_tri(exe, tmp_path, p):
     m = np.ascontiguousarray(p["matches"], TR.MATCH_DTYPE)
     blob = b"".join([np.asarray(p["kf1"], TR.KEYFRAME_DTYPE).tobytes(), np.asarray(p["kf2"], TR.KEYFRAME_DTYPE).tobytes(),
                      np.array([p["ratio_factor"], 0], F).tobytes(), np.asarray(p["state_cov"], D).tobytes(),
                      np.array([p["th_confidence"], p["th_entropy"]], D).tobytes(), np.array([m.shape[0]], np.int64).tobytes(), m.tobytes()])
-    fin, fout = tmp_path / "tri.in", tmp_path / "tri.out"
-    fin.write_bytes(blob)
-    r = subprocess.run([exe, "tri", str(fin), str(fout)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
-    raw, n = fout.read_bytes(), m.shape[0]
+    raw, n = host_prog.run(exe, tmp_path, "tri", blob, timeout=120), m.shape[0]
     assert len(raw) == 14 * n
     return {"status": np.frombuffer(raw, np.uint8, n), "detected_class": np.frombuffer(raw, np.uint8, n, n),
             "wP": np.frombuffer(raw, F, 3 * n, 2 * n).reshape(n, 3)}
@@ -49,11 +36,7 @@ def run_refresh(exe, tmp_path, s):
     rec = np.concatenate([s["pos"], s["ref_ow"], s["level_scale"][:, None], s["last_scale"][:, None]], axis=1).astype(F)
     blob = b"".join([np.array([n], np.int64).tobytes(), np.asarray(s["desc_off"], np.int64).tobytes(), np.asarray(s["obs_off"], np.int64).tobytes(),
                      np.ascontiguousarray(s["desc"], np.uint8).tobytes(), np.ascontiguousarray(s["obs_ow"], F).tobytes(), rec.tobytes()])
-    fin, fout = tmp_path / "mp.in", tmp_path / "mp.out"
-    fin.write_bytes(blob)
-    r = subprocess.run([exe, "refresh", str(fin), str(fout)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
-    raw = fout.read_bytes()
+    raw = host_prog.run(exe, tmp_path, "refresh", blob, timeout=120)
     assert len(raw) == 25 * n
     geom = np.frombuffer(raw, F, 5 * n, 4 * n).reshape(n, 5)
     best = np.frombuffer(raw, np.int32, n).copy()
@@ -104,13 +87,14 @@ def check_host(exe, tmp_path):
 
 
 def test_host_build_of_the_kernel_arithmetic_equals_the_restatement(tmp_path):
-    check_host(build_prog(tmp_path), tmp_path)
+    check_host(host_prog.build("local_mapping_prog", tmp_path), tmp_path)
 
 
 def test_host_build_under_address_and_undefined_sanitizers(tmp_path):
     """The same stand-alone program built with -fsanitize=address,undefined and run directly: no finding, the same bytes."""
-    exe = build_prog(tmp_path, ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
-    check_host(exe, tmp_path)
+    if not host_prog.sanitizer_runtime_present(tmp_path):
+        pytest.skip("the sanitizer runtime (libasan / libubsan) is not installed: a trivial main does not link with -fsanitize")
+    check_host(host_prog.build("local_mapping_prog", tmp_path, sanitize=True), tmp_path)
 
 
 def test_the_sweep_count_is_read_from_the_source():
@@ -227,19 +211,8 @@ def test_header_declares_and_library_exports_the_entry_points():
 
 def test_ctypes_structs_and_dtypes_match_the_header(tmp_path):
     from sivo_amd import _lib, local_mapping
-    pairs = (("SivoTriKeyFrame", _lib.TriKeyFrame), ("SivoTriMatch", _lib.TriMatch), ("SivoTriProblem", _lib.TriProblem))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sivo_hip.h"\nint main(void) {\n'
-                   + "".join(f'  printf(" %zu", sizeof({c}));\n' + "".join(f'  printf(" %zu", offsetof({c}, {f[0]}));\n' for f in t._fields_)
-                             for c, t in pairs) + "  return 0;\n}\n")
-    exe = str(tmp_path / "sz")
-    r = subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split()]
-    want = []
-    for _, t in pairs:
-        want += [C.sizeof(t)] + [getattr(t, f[0]).offset for f in t._fields_]
-    assert got == want
+    for c, t in (("SivoTriKeyFrame", _lib.TriKeyFrame), ("SivoTriMatch", _lib.TriMatch), ("SivoTriProblem", _lib.TriProblem)):
+        host_prog.c_layout(tmp_path, c, t)
     for dt, t in ((local_mapping.KEYFRAME_DTYPE, _lib.TriKeyFrame), (local_mapping.MATCH_DTYPE, _lib.TriMatch)):
         assert [dt.fields[f[0]][1] for f in t._fields_] == [getattr(t, f[0]).offset for f in t._fields_]
 
@@ -304,7 +277,6 @@ def test_entry_points_check_arguments_and_fail_loudly_without_a_device():
 # ---------------------------------------------------------------------------------------------------------------------
 # SIVO::CreateNewMapPoints / TriangulateMatches / RefreshMapPoints
 # ---------------------------------------------------------------------------------------------------------------------
-ADAPTER_PROG = os.path.join(ROOT, "tests", "local_mapping_adapter_prog.cpp")
 SNIPPETS = {
     # LocalMapping.cc:198-472 as LocalMapping::Run calls it (:71-72)
     "create_new_map_points": r'''int f(LKeyFrame *mpCurrentKeyFrame, std::vector<LKeyFrame *> vpNeighKFs, LMap *mpMap, std::list<LMapPoint *> &mlpRecentAddedMapPoints, bool mbMonocular) {
@@ -329,13 +301,8 @@ def test_adapter_instantiates_over_stand_in_types(tmp_path, snippet):
     assert r.returncode == 0, r.stderr[-3000:]
 
 
-def build_adapter_prog(tmp_path):
-    exe = str(tmp_path / "local_mapping_adapter_prog")
-    lib = os.path.join(ROOT, "sivo_amd")
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-I" + API, "-I" + os.path.join(ROOT, "tests"), ADAPTER_PROG, "-o", exe, "-L" + lib,
-                        "-lsivo_api", "-lsivo_hip", "-Wl,-rpath," + lib], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+def adapter_prog(out_dir, defines=()):
+    return host_prog.build("local_mapping_adapter_prog", out_dir, link_lib=("sivo_api", "sivo_hip"), defines=defines)
 
 
 def tri_blob(p):
@@ -360,11 +327,9 @@ def test_adapter_gathers_the_records_of_the_reference_walk(tmp_path):
     """gather_matches over stand-in keyframes whose keys are the scene's keypoints (keyframe 2's in reverse order): the staged problem is
     the scene, byte for byte — keypoints, octaves, mvRight, mvDepth and the four semantic lookups at the truncated positions."""
     p = adapter_problem()
-    exe = build_adapter_prog(tmp_path)
-    fin, fout = tmp_path / "g.in", tmp_path / "g.out"
-    fin.write_bytes(tri_blob(p))
-    r = subprocess.run([exe, "gather", str(fin), str(fout)], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, (r.returncode, r.stderr)
+    exe = adapter_prog(tmp_path)
+    fout = tmp_path / "gather.out"
+    host_prog.run(exe, tmp_path, "gather", tri_blob(p), timeout=60)                 # (writes fout)
     assert fout.read_bytes() == tri_blob(p)
 
 
@@ -492,11 +457,9 @@ def test_adapter_walks_the_neighbours_as_the_reference_does(tmp_path, checks):
     of :230-259, :471 in Python: neighbour 0 is skipped for its baseline, the pairs neighbour 2's search is given depend on the points
     neighbour 1 made, checkNewKeyFrames() ends the loop (checks = 1: before the last neighbour), and F12 is ComputeF12's, bit for bit."""
     sc = map_scene()
-    exe = build_adapter_prog(tmp_path)
-    fin, fout = tmp_path / "w.in", tmp_path / "w.out"
-    fin.write_bytes(map_blob(sc, checks))
-    r = subprocess.run([exe, "walk", str(fin), str(fout)], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, (r.returncode, r.stderr)
+    exe = adapter_prog(tmp_path)
+    fout = tmp_path / "walk.out"
+    host_prog.run(exe, tmp_path, "walk", map_blob(sc, checks), timeout=60)          # (writes fout)
     # the literal walk
     frames = sc["frames"]
     n = len(frames[0][1])

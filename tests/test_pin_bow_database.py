@@ -9,7 +9,6 @@ the device were written from one reading of that source; this file holds each of
 Where the reference is absent the same assertions read tests/golden/bowdb_reference.npz (tests/golden/make_bowdb_reference.py wrote it
 from the live run); the tests marked gpu read only the fixture."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,11 +16,11 @@ import pytest
 from conftest import ROOT
 import bow_restatement as BR
 import bowdb_pin_cases as P
+import host_prog
 import test_bow_host as BH
 import solver_pin_cases as S
 
 F = np.float32
-LIB = os.path.join(ROOT, "sivo_amd")
 
 
 def same_trace(want, got, what):
@@ -132,19 +131,9 @@ def test_reference_driver_under_address_and_undefined_sanitizers():
 # ---------------------------------------------------------------------------------------------------------------------
 # the host path under SIVO::KeyFrameDatabase
 # ---------------------------------------------------------------------------------------------------------------------
-def build_adapter(out_dir, on_host):
-    exe = os.path.join(str(out_dir), "bow_adapter_prog" + ("_host" if on_host else ""))
-    cmd = ["g++", "-std=c++14", "-O2", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", "-I" + os.path.join(LIB, "api"), "-I" + os.path.join(ROOT, "tests")]
-    cmd += ["-DSIVO_BOW_ON_HOST", "-I" + os.path.join(LIB, "csrc")] if on_host else []
-    cmd += [os.path.join(ROOT, "tests", "bow_adapter_prog.cpp"), "-o", exe] + ([] if on_host else ["-L" + LIB, "-lsivo_hip", "-Wl,-rpath," + LIB])
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def host_adapter(tmp_path_factory):
-    return build_adapter(tmp_path_factory.mktemp("host_adapter"), True)
+    return host_prog.build("bow_adapter_prog", tmp_path_factory.mktemp("host_adapter"), defines=("SIVO_BOW_ON_HOST",))
 
 
 def check_adapter(exe, name, tmp_path, trace):
@@ -250,7 +239,7 @@ class ProgStore(PlainStore):
 
 @pytest.fixture(scope="module")
 def bow_prog(tmp_path_factory):
-    return BH.build_prog(tmp_path_factory.mktemp("bow_prog"))
+    return host_prog.build("bow_prog", tmp_path_factory.mktemp("bow_prog"))
 
 
 @pytest.mark.parametrize("name", P.NAMES)
@@ -263,7 +252,7 @@ def test_bow_prog_query_gives_the_references_counts_and_scores(bow_prog, tmp_pat
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def device_adapter(tmp_path_factory):
-    return build_adapter(tmp_path_factory.mktemp("device_adapter"), False)
+    return host_prog.build("bow_adapter_prog", tmp_path_factory.mktemp("device_adapter"), link_lib=True)
 
 
 @pytest.mark.gpu

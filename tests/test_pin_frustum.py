@@ -10,13 +10,14 @@ import numpy as np
 import pytest
 
 import frustum_pin_cases as P
+import host_prog
 
 F32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def prog(tmp_path_factory):
-    return P.build_prog(tmp_path_factory.mktemp("frustum_prog"))
+    return host_prog.build("frustum_prog", tmp_path_factory.mktemp("frustum_prog"))
 
 
 def sources():
@@ -87,9 +88,9 @@ def test_sanitizer_build_of_the_program_agrees(prog, tmp_path, tmp_path_factory)
     """The stand-alone program built a second time with -fsanitize=address,undefined and run directly (it has its own main: nothing is
     preloaded), every mode: the same bytes as the plain build, and no report."""
     san_dir = tmp_path_factory.mktemp("frustum_prog_san")
-    if not P.sanitizer_runtime_present(san_dir):
+    if not host_prog.sanitizer_runtime_present(san_dir):
         pytest.skip("the sanitizer runtime (libasan / libubsan) is not installed: a trivial main does not link with -fsanitize")
-    san = P.build_prog(san_dir, sanitize=True)
+    san = host_prog.build("frustum_prog", san_dir, sanitize=True)
     for group in P.GROUPS:
         for mode in ("cull", "isinfrustum"):
             a, b = P.host_cull(prog, tmp_path, group, mode=mode), P.host_cull(san, tmp_path, group, mode=mode)

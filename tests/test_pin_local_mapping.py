@@ -19,6 +19,7 @@ Still substitutions (DESIGN.md §5): cv::SVD::compute and cv::Mat::inv (oracle/c
 routines byte for byte), KeyFrame::UnprojectStereo, the scripted SearchForTriangulation.
 Where the reference is absent the same assertions read tests/golden/local_mapping_reference.npz; the tests marked gpu read only that file."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -26,6 +27,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import host_prog as hp                   # (host_prog is a fixture's name below)
 import local_mapping_pin_cases as P
 import mappoint_restatement as MR
 import solver_pin_cases as S
@@ -141,7 +143,7 @@ def test_search_in_neighbors_equals_the_line_by_line_walk(name):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_prog(tmp_path_factory):
-    return H.build_prog(tmp_path_factory.mktemp("local_mapping_prog"))
+    return hp.build("local_mapping_prog", tmp_path_factory.mktemp("local_mapping_prog"))
 
 
 def test_host_build_equals_the_reference(host_prog, tmp_path):
@@ -276,33 +278,17 @@ def test_device_mappoint_refresh_equals_the_recorded_reference():
 # the C++ adapter (sivo_amd/api/orbslam/LocalMappingAdapter.h) through tests/local_mapping_adapter_prog.cpp: over the host build of the
 # kernels' arithmetic (tests/local_mapping_host_capi.hpp) against the live or recorded reference, and on the device against the recorded one
 # ---------------------------------------------------------------------------------------------------------------------
-def build_adapter(out_dir, on_host):
-    if not on_host:
-        return H.build_adapter_prog(out_dir)
-    exe, lib = str(out_dir / "local_mapping_adapter_prog_host"), os.path.join(ROOT, "sivo_amd")
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", "-DSIVO_LM_ON_HOST", "-I" + H.API, "-I" + H.CSRC,
-                        "-I" + os.path.join(ROOT, "tests"), H.ADAPTER_PROG, "-o", exe, "-L" + lib, "-lsivo_api", "-lsivo_hip", "-Wl,-rpath," + lib],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def adapter_prog(tmp_path_factory):
-    return build_adapter(tmp_path_factory.mktemp("local_mapping_adapter_prog"), False)
+    return H.adapter_prog(tmp_path_factory.mktemp("local_mapping_adapter_prog"))
 
 
 @pytest.fixture(scope="module")
 def adapter_prog_host(tmp_path_factory):
-    return build_adapter(tmp_path_factory.mktemp("local_mapping_adapter_prog_host"), True)
+    return H.adapter_prog(tmp_path_factory.mktemp("local_mapping_adapter_prog_host"), defines=("SIVO_LM_ON_HOST",))
 
 
-def run_adapter(exe, tmp_path, mode, blob):
-    fin, fout = tmp_path / "a.in", tmp_path / "a.out"
-    fin.write_bytes(blob)
-    r = subprocess.run([exe, mode, str(fin), str(fout)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (mode, r.returncode, r.stderr[-2000:])
-    return fout.read_bytes()
+run_adapter = functools.partial(hp.run, timeout=120)
 
 
 def check_cpp_walk(exe, tmp_path, name, want):

@@ -23,11 +23,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import host_prog
 import pnp_ransac_restatement as RP
 import sim3_ransac_restatement as RS
 import solver_pin_cases as S
 import test_pnp_ransac_host as HP
-import test_sim3_ransac_host as HS
 import test_gpu_pnp_ransac as GP
 import test_gpu_sim3_ransac as GS
 
@@ -310,7 +310,7 @@ SCENE_HYPOTHESES = {name: row[1] for name, row in GP.SCENES.items()}
 
 @pytest.fixture(scope="module")
 def pnp_prog(tmp_path_factory):
-    return HP.build_prog(tmp_path_factory.mktemp("pnp_prog"))
+    return host_prog.build("pnp_ransac_prog", tmp_path_factory.mktemp("pnp_prog"), link_lib=True)
 
 
 @pytest.mark.parametrize("name", list(GP.SCENES))
@@ -320,9 +320,7 @@ def test_pnp_host_build_of_the_kernel_arithmetic_equals_the_reference(name, pnp_
     sc = GP.scene(name)
 
     def run(sets):
-        r = subprocess.run([pnp_prog, "core64"], input=HP.core_text(sc["pts"], sc["K"], sets), capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stderr
-        return r.stdout
+        return host_prog.run_text(pnp_prog, ["core64"], HP.core_text(sc["pts"], sc["K"], sets), 120)
     got = S.pnp_core(sc, run)
     count, refined = got["counts"][:, 0], got["counts"][:, 1]
     rec = np.flatnonzero(refined >= 0)
@@ -554,7 +552,7 @@ def test_cpp_pnpsolver_reproduces_the_reference_transcripts(pnp_prog):
 @pytest.mark.gpu
 def test_cpp_sim3solver_reproduces_the_reference_transcripts(tmp_path):
     """SIVO::Sim3Solver over libsivo_hip.so (tests/sim3_ransac_prog.cpp run) on every case that program's protocol can express."""
-    exe = HS.build_prog(tmp_path)
+    exe = host_prog.build("sim3_ransac_prog", tmp_path, link_lib=True)
     plain = [n for n in S.SIM3_RUN_CASES if S.sim3_run_case(n).get("plain")]
     assert plain == ["round_robin", "equal_min", "too_few"]
     for name in plain:

@@ -12,11 +12,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import host_prog
 import pnp_ransac_restatement as R
 
 API = os.path.join(ROOT, "sivo_amd", "api")
 CSRC = os.path.join(ROOT, "sivo_amd", "csrc")
-PROG = os.path.join(ROOT, "tests", "pnp_ransac_prog.cpp")
 
 # EPnP on exact correspondences, the restatement against the LAPACK form (lapack_epnp below) and against the true pose, measured
 # here on the CPU over 6 seeds x 300 samples of the generator's noise-free scenes (seeds 11 .. 16, 60 points, every sample
@@ -372,15 +372,6 @@ def test_degenerate_samples_count_nothing():
 # ---------------------------------------------------------------------------------------------------------------------
 # the kernel's arithmetic, compiled for the host
 # ---------------------------------------------------------------------------------------------------------------------
-def build_prog(tmp_path):
-    exe = str(tmp_path / "pnp_ransac_prog")
-    lib = os.path.join(ROOT, "sivo_amd")
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-ffp-contract=off", "-I" + API, "-I" + CSRC, PROG, "-o", exe, "-L" + lib,
-                        "-lsivo_hip", "-Wl,-rpath," + lib], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 def core_text(pts, K, sets):
     out = [str(len(pts)), " ".join(float(np.float32(v)).hex() for v in K)]
     out += [" ".join(float(v).hex() for v in (*p["xw"], p["u"], p["v"], p["max_err"])) for p in pts]
@@ -392,7 +383,7 @@ def core_text(pts, K, sets):
 def test_host_build_of_the_kernel_arithmetic_equals_the_restatement(tmp_path):
     """pnp_epnp.hpp with a team of one lane (g++, no contraction) against the restatement: samples of 4, refinement sets of other
     sizes, a duplicated and a coplanar scene (NaN poses)."""
-    exe = build_prog(tmp_path)
+    exe = host_prog.build("pnp_ransac_prog", tmp_path, link_lib=True)
     nans = 0
     for seed, n, kw in ((1, 70, dict(outliers=0.3)), (3, 40, dict(duplicates=5)), (4, 50, dict(coplanar=True))):
         sc = R.make_scene(seed, n, **kw)
@@ -400,9 +391,7 @@ def test_host_build_of_the_kernel_arithmetic_equals_the_restatement(tmp_path):
         res = R.pnp_ransac(sc["pts"], sc["K"], S, 8)
         rec = np.flatnonzero(res["refined"] >= 0)
         sets = [list(s) for s in S] + [list(np.flatnonzero(R.unpack_bits(res["inlier_bits"][h], n))) for h in rec]
-        r = subprocess.run([exe, "core"], input=core_text(sc["pts"], sc["K"], sets), capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stderr
-        rows = [ln.split() for ln in r.stdout.strip().splitlines()]
+        rows = [ln.split() for ln in host_prog.run_text(exe, ["core"], core_text(sc["pts"], sc["K"], sets), 120).strip().splitlines()]
         T = np.array([[float.fromhex(v) for v in w[1:13]] for w in rows])
         T = R.store_T(T[:, :9], T[:, 9:])
         want_T = np.concatenate([res["T"], res["refined_T"][rec]])
@@ -429,20 +418,9 @@ def test_header_declares_and_library_exports_the_entry_points():
 
 def test_ctypes_structs_match_the_header(tmp_path):
     from sivo_amd import _lib
-    src = tmp_path / "sz.c"
-    fields = [f[0] for f in _lib.PnpRansacProblem._fields_]
-    pf = [f[0] for f in _lib.PnpPoint._fields_]
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sivo_hip.h"\nint main(void) {\n'
-                   '  printf("%zu %zu", sizeof(SivoPnpPoint), sizeof(SivoPnpRansacProblem));\n'
-                   + "".join(f'  printf(" %zu", offsetof(SivoPnpRansacProblem, {f}));\n' for f in fields)
-                   + "".join(f'  printf(" %zu", offsetof(SivoPnpPoint, {f}));\n' for f in pf) + "  return 0;\n}\n")
-    exe = str(tmp_path / "sz")
-    r = subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split()]
-    want = ([C.sizeof(_lib.PnpPoint), C.sizeof(_lib.PnpRansacProblem)] + [getattr(_lib.PnpRansacProblem, f).offset for f in fields]
-            + [getattr(_lib.PnpPoint, f).offset for f in pf])
-    assert got == want and got[0] == 24
+    host_prog.c_layout(tmp_path, "SivoPnpPoint", _lib.PnpPoint)
+    host_prog.c_layout(tmp_path, "SivoPnpRansacProblem", _lib.PnpRansacProblem)
+    assert C.sizeof(_lib.PnpPoint) == 24
 
 
 def test_entry_points_check_arguments_and_fail_loudly_without_a_device():
@@ -556,10 +534,8 @@ def frame_text(fr):
 
 def test_gather_matches_the_reference_walk(tmp_path):
     fr = make_frame(8, 30)
-    exe = build_prog(tmp_path)
-    r = subprocess.run([exe, "gather"], input="1\n" + frame_text(fr), capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    rows = [ln.split() for ln in r.stdout.strip().splitlines()]
+    exe = host_prog.build("pnp_ransac_prog", tmp_path, link_lib=True)
+    rows = [ln.split() for ln in host_prog.run_text(exe, ["gather"], "1\n" + frame_text(fr), 60).strip().splitlines()]
     pts, idx, _ = R.gather(fr)
     assert [int(w[1]) for w in rows] == list(idx) and len(idx) == 30 and len(fr["matches"]) == 40
     assert (fr["matches"] < 0).sum() == 5 and fr["bad"].sum() == 5           # null and bad entries among the matches

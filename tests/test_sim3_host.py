@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import host_prog
 import sim3_restatement as R
 
 API = os.path.join(ROOT, "sivo_amd", "api")
-PROG = os.path.join(ROOT, "tests", "sim3_adapter_prog.cpp")
 
 
 def _close(A, B, tol):
@@ -117,26 +117,12 @@ int f(KF *a, KF *b, std::vector<MP *> &m, S3 &s) { return SIVO::Optimizer::Optim
     assert r.returncode == 0, r.stderr[-3000:]
 
 
-def build_prog(tmp_path, device):
-    exe = str(tmp_path / ("sim3_prog_dev" if device else "sim3_prog"))
-    cmd = ["g++", "-std=c++14", "-O2", "-Wall", "-I" + API, PROG, "-o", exe]
-    if device:
-        lib = os.path.join(ROOT, "sivo_amd")
-        cmd[4:4] = ["-DSIVO_SIM3_ON_DEVICE"]
-        cmd += ["-L" + lib, "-lsivo_hip", "-Wl,-rpath," + lib]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.mark.parametrize("random_pose", [False, True])
 def test_gather_matches_the_reference_walk(tmp_path, random_pose):
     sc = R.make_scene(30, 8)
     kf1, kf2, pts, m1 = R.keyframe_pair(sc, 9, random_pose=random_pose, n_extra=15)
-    exe = build_prog(tmp_path, False)
-    r = subprocess.run([exe, "gather"], input=R.scene_text(sc, kf1, kf2, pts, m1), capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    rows = [ln.split() for ln in r.stdout.strip().splitlines()]
+    exe = host_prog.build("sim3_adapter_prog", tmp_path)
+    rows = [ln.split() for ln in host_prog.run_text(exe, ["gather"], R.scene_text(sc, kf1, kf2, pts, m1), 60).strip().splitlines()]
     idx, recs = R.gather(kf1, kf2, m1, pts)
     assert [int(w[0]) for w in rows] == list(idx)
     assert len(idx) == 30                                    # every pair of the scene, none of the 15 entries to skip

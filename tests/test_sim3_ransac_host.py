@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import host_prog
 import sim3_ransac_restatement as R
 
 API = os.path.join(ROOT, "sivo_amd", "api")
-PROG = os.path.join(ROOT, "tests", "sim3_ransac_prog.cpp")
 
 # Horn on exact correspondences in float32.  The inputs carry a relative rounding of 2^-24 = 6e-8 on coordinates up to ~35; the
 # rotation comes from differences to the centroid, so its error is that rounding divided by the relative spread of the sample
@@ -191,17 +191,9 @@ def test_header_declares_and_library_exports_the_entry_points():
 
 def test_ctypes_structs_match_the_header(tmp_path):
     from sivo_amd import _lib
-    src = tmp_path / "sz.c"
-    fields = [f[0] for f in _lib.Sim3RansacProblem._fields_]
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sivo_hip.h"\nint main(void) {\n'
-                   '  printf("%zu %zu", sizeof(SivoSim3Pair), sizeof(SivoSim3RansacProblem));\n'
-                   + "".join(f'  printf(" %zu", offsetof(SivoSim3RansacProblem, {f}));\n' for f in fields) + "  return 0;\n}\n")
-    exe = str(tmp_path / "sz")
-    r = subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split()]
-    want = [C.sizeof(_lib.Sim3Pair), C.sizeof(_lib.Sim3RansacProblem)] + [getattr(_lib.Sim3RansacProblem, f).offset for f in fields]
-    assert got == want and got[0] == 32
+    host_prog.c_layout(tmp_path, "SivoSim3Pair", _lib.Sim3Pair)
+    host_prog.c_layout(tmp_path, "SivoSim3RansacProblem", _lib.Sim3RansacProblem)
+    assert C.sizeof(_lib.Sim3Pair) == 32
 
 
 def test_entry_points_check_arguments_and_fail_loudly_without_a_device():
@@ -280,23 +272,13 @@ def test_class_instantiates_over_stand_in_types(tmp_path, snippet):
     assert r.returncode == 0, r.stderr[-3000:]
 
 
-def build_prog(tmp_path):
-    exe = str(tmp_path / "sim3_ransac_prog")
-    lib = os.path.join(ROOT, "sivo_amd")
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-I" + API, PROG, "-o", exe, "-L" + lib, "-lsivo_hip", "-Wl,-rpath," + lib],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.mark.parametrize("random_pose", [False, True])
 def test_gather_matches_the_reference_walk(tmp_path, random_pose):
     sc = R.make_scene(30, 8)
     kf1, kf2, pts, m12 = R.keyframe_pair(sc, 9, random_pose=random_pose, n_extra=18)
-    exe = build_prog(tmp_path)
-    r = subprocess.run([exe, "gather"], input="1\n" + R.scene_text(sc, kf1, kf2, pts, m12, True), capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    rows = [ln.split() for ln in r.stdout.strip().splitlines()]
+    exe = host_prog.build("sim3_ransac_prog", tmp_path, link_lib=True)
+    out = host_prog.run_text(exe, ["gather"], "1\n" + R.scene_text(sc, kf1, kf2, pts, m12, True), 60)
+    rows = [ln.split() for ln in out.strip().splitlines()]
     idx, recs = R.gather(kf1, kf2, m12, pts)
     assert [int(w[1]) for w in rows] == list(idx)
     assert len(idx) == 30 and len(m12) == 48                 # every pair of the scene, none of the 18 entries to skip

@@ -21,6 +21,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import host_prog  # noqa: E402
 
 
 def full_voc(k, L, seed=1):
@@ -100,9 +102,7 @@ def main():
         emit("sivo_bowdb_query", stored=stored, words_per_vector=1000, median_shared_words=shared, **timed(lambda: db.query(*q), a.reps))
     # the host build of the same arithmetic, the same shapes
     with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "bow_prog")
-        subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-I" + os.path.join(ROOT, "sivo_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "bow_prog.cpp"), "-o", exe], check=True, timeout=300)
+        exe = host_prog.build("bow_prog", tmp)
         for stored in (300, 1000, 2000):
             out = subprocess.run([exe, "bench", str(k), str(L), str(n), str(stored), "1000"], check=True, capture_output=True, text=True, timeout=600).stdout
             for ln in out.splitlines():

@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import covis_cases as P  # noqa: E402
+import host_prog  # noqa: E402
 from sivo_amd import _lib, covisibility as cov  # noqa: E402
 
 N_KF, N_LOCAL, SLOTS, N_POINTS, N_FRAME, N_RECENT, CURRENT_ID = 100, 80, 2000, 12000, 1500, 400, 500
@@ -133,10 +134,10 @@ def main():
     # the same on the host: the reference's walk over the stand-in object graph
     with tempfile.TemporaryDirectory() as d:
         d = pathlib.Path(d)
-        exe = P.build_prog(d, "covis_adapter_prog")
+        exe = host_prog.build("covis_adapter_prog", d)
         blob = b"".join([graph, P.i32(0, K), local.tobytes(), P.i32(N_FRAME), sc["frame"].tobytes(), np.array([CURRENT_ID], np.int64).tobytes(),
                          P.i32(len(r)), r.tobytes(), P.i32(a.walk_repeats)])
-        walk = np.frombuffer(P.run_prog(exe, d, "walk", blob), np.float64)[:4] / 1e3
+        walk = np.frombuffer(host_prog.run(exe, d, "walk", blob), np.float64)[:4] / 1e3
     host = dict(zip(("keyframe_culling", "vote", "update_connections", "map_point_culling"), (round(float(x), 4) for x in walk)))
     print(json.dumps(dict(shape=dict(n_kf=N_KF, n_local=K, slots_per_keyframe=SLOTS, n_points=int(table.n_points), n_observations=int(len(table.obs_kf)),
                                      frame_slots=N_FRAME, recent_points=int(len(r))),
