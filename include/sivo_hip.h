@@ -1049,6 +1049,77 @@ int sivo_mappoint_culling(int n, const int32_t *found, const int32_t *visible, c
                           const int32_t *n_obs, const uint8_t *bad, int64_t current_kf_id, int monocular, uint8_t *status);
 
 /* ===========================================================================
+ * The tracking thread's local map: Tracking::UpdateLocalMap (reference
+ * src/orbslam/Tracking.cc:1087-1235) — the vote, mvpLocalKeyFrames, mpReferenceKF
+ * and mvpLocalMapPoints — on a map that stays resident on the device between the
+ * frames.  Integer work, exact, the reference's order everywhere.  DESIGN 3.6i.
+ * ======================================================================== */
+typedef struct sivo_localmap *sivo_localmap_t;
+
+typedef struct {
+    int32_t n_kf;              /* keyframes and points are dense indices chosen by the caller */
+    int32_t n_points;
+    const int64_t *obs_off;    /* n_points + 1, CSR over mObservations (as in SivoObsTable) */
+    const int32_t *obs_kf;
+    const uint8_t *point_bad;  /* n_points: MapPoint::isBad() */
+    const uint8_t *kf_bad;     /* n_kf: KeyFrame::isBad() */
+    const int64_t *slot_off;   /* n_kf + 1, CSR over GetMapPointMatches() in slot order */
+    const int32_t *slot_point; /* -1 for a null slot */
+    const int64_t *covis_off;  /* n_kf + 1, CSR over mvpOrderedConnectedKeyFrames in its order, bad keyframes included; */
+    const int32_t *covis_kf;   /* only the first 10 of a list are read (GetBestCovisibilityKeyFrames(10), KeyFrame.cc:222-230) */
+    const int64_t *child_off;  /* n_kf + 1, CSR over mspChildren in the order the std::set iterates */
+    const int32_t *child_kf;
+    const int32_t *parent;     /* n_kf: mpParent, -1 for none */
+    const int32_t *kf_order;   /* n_kf, a permutation: the order in which std::map<KeyFrame *, int> walks the keyframes
+                                  (Tracking.cc:1156: by pointer value); NULL = 0, 1, 2 ... */
+} SivoLocalMapTables;
+
+/* The tables go to the device once and stay there.  For create, replace, set_bad and
+ * update: an offset array that does not start at 0 or that decreases, an index outside
+ * its range, a kf_order that is not a permutation, a negative count or a NULL array
+ * with a non-zero count -> SIVO_ERR_INVALID_ARGUMENT before any device is touched.
+ * A handle serves one call at a time (calls from several threads are serialised). */
+int sivo_localmap_create(const SivoLocalMapTables *t, sivo_localmap_t *map);
+/* A new set of tables into the same handle; its device buffers are reused when they
+ * are large enough. */
+int sivo_localmap_replace(sivo_localmap_t map, const SivoLocalMapTables *t);
+/* point_bad[point_idx[i]] = point_val[i] and kf_bad[kf_idx[i]] = kf_val[i]: all the
+ * other threads change between two rebuilds of the map that the update reads.  Of an
+ * index listed twice the later entry holds. */
+int sivo_localmap_set_bad(sivo_localmap_t map, int n_points, const int32_t *point_idx, const uint8_t *point_val, int n_kf,
+                          const int32_t *kf_idx, const uint8_t *kf_val);
+int sivo_localmap_destroy(sivo_localmap_t map);
+
+/* Tracking::UpdateLocalMap (Tracking.cc:1092-1093: UpdateLocalKeyFrames :1126-1235,
+ * then UpdateLocalPoints :1096-1124) for one frame: one upload, the launches, one
+ * download, one synchronisation.
+ * In: frame_point (n_slots = numSemanticKeys) = mCurrentFrame.mvpMapPoints as point
+ * indices, -1 for null; kf_premarked / point_premarked = the keyframes / points whose
+ * mnTrackReferenceForFrame already equals the frame's id (either may be NULL with a
+ * count of 0); prev_local_kf = the mvpLocalKeyFrames the caller holds.
+ * Out: *voted = 0 where keyframeCounter is empty (:1144): then local_kf and
+ * *n_local_kf are not written, *ref_kf = -1 and the points are those of prev_local_kf,
+ * as UpdateLocalPoints still runs.  slot_cleared[i] = 1 where the reference sets
+ * mvpMapPoints[i] = nullptr (:1138-1140), else 0.  local_kf[0 .. *n_local_kf) =
+ * mvpLocalKeyFrames: every voted keyframe that is not bad in kf_order (:1156-1172, not
+ * capped), then for each of those, while the list holds no more than 80 (:1183), the
+ * first of its first ten covisibles and the first of its children that are neither bad
+ * nor marked, and its parent if not marked (isBad() not tested) — after the first
+ * parent the loop ends (:1222-1228).  *ref_kf = pKFmax, the first strict maximum in
+ * kf_order among the voted keyframes that are not bad; -1 leaves mpReferenceKF alone.
+ * local_point[0 .. *n_local_points) = mvpLocalMapPoints: over the local keyframes in
+ * order and their slots in order, the first occurrence of every point that is neither
+ * premarked nor bad.  counts (n_kf, may be NULL) = keyframeCounter, 0 where absent.
+ * Entries past the counts returned are left as the caller had them.  A list longer than
+ * kf_capacity / point_capacity -> SIVO_ERR_CAPACITY and no output is written.
+ * The result depends on the handle's tables and this call's arguments alone. */
+int sivo_localmap_update(sivo_localmap_t map, int n_slots, const int32_t *frame_point, int n_kf_premarked,
+                         const int32_t *kf_premarked, int n_point_premarked, const int32_t *point_premarked, int n_prev,
+                         const int32_t *prev_local_kf, int32_t *voted, uint8_t *slot_cleared, int kf_capacity,
+                         int32_t *local_kf, int32_t *n_local_kf, int32_t *ref_kf, int point_capacity, int32_t *local_point,
+                         int32_t *n_local_points, int32_t *counts);
+
+/* ===========================================================================
  * Place recognition: the bag-of-words vocabulary and the keyframe database —
  * DBoW2 as ORB-SLAM2 uses it (reference dependencies/DBoW2/DBoW2/TemplatedVocabulary.h,
  * src/orbslam/KeyFrameDatabase.cc:72-322).  Only L1_NORM scoring with TF_IDF

@@ -219,6 +219,11 @@ SIGNATURES = {
     "sivo_covis_count": [_vp, _i, _vp, _vp, _vp, _vp],
     "sivo_keyframe_culling": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "sivo_mappoint_culling": [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp],
+    "sivo_localmap_create": [_vp, C.POINTER(_vp)],
+    "sivo_localmap_replace": [_vp, _vp],
+    "sivo_localmap_set_bad": [_vp, _i, _vp, _vp, _i, _vp, _vp],
+    "sivo_localmap_destroy": [_vp],
+    "sivo_localmap_update": [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp],
     "sivo_voc_create_from_text": [C.c_char_p, C.POINTER(_vp)],
     "sivo_voc_create": [_i, _i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_vp)],
     "sivo_voc_info": [_vp, _pi32, _pi32, C.POINTER(_i64), C.POINTER(_i64)],

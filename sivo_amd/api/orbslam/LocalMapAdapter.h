@@ -1,0 +1,187 @@
+// Tracking::UpdateLocalMap (reference src/orbslam/Tracking.cc:1087-1235) over the SLAM object graph, on a map that stays on the device:
+//     SIVO::LocalMapDevice<KeyFrame, MapPoint> dev;           owns a sivo_localmap_t and the pointer <-> index maps
+//     dev.Rebuild(vpAllKFs)                                   gathers the tables of include/sivo_hip.h once and uploads them
+//     dev.MarkBad(pKF) / dev.MarkBad(pMP)                     isBad() of one keyframe / point became true since the last Rebuild
+//     SIVO::UpdateLocalMap(dev, F, vpLocalKeyFrames, vpLocalMapPoints, pReferenceKF)
+//                                                             in place of UpdateLocalKeyFrames(); UpdateLocalPoints(); (:1092-1093)
+// as header-only templates.  UpdateLocalMap maps F.mvpMapPoints to indices, makes ONE call to sivo_localmap_update and writes back as the
+// reference does: the cleared slots of the frame (:1139), both vectors, mnTrackReferenceForFrame of every listed keyframe and point
+// (:1120, :1171, :1200, :1215, :1225), and pReferenceKF and F.mpReferenceKF where a keyframe had the most votes (:1231-1234).
+//
+// KeyFrame, MapPoint and Frame are template parameters (SLAM data model, outside this library — SURVEY.md 8).  The members read, all the
+// reference's own: KeyFrame: GetMapPointMatches, GetVectorCovisibleKeyFrames (mvpOrderedConnectedKeyFrames; the first ten are used,
+// KeyFrame.cc:222-230), GetChildren, GetParent, isBad, mnTrackReferenceForFrame; MapPoint: GetObservations, isBad,
+// mnTrackReferenceForFrame; Frame: mnId, numSemanticKeys, mvpMapPoints, mpReferenceKF.
+//
+// kf_order, the order in which the reference's std::map<KeyFrame *, int> walks (:1156), is std::less<KeyFrame *> over the pointers; the
+// children are listed as the std::set iterates.  A frame slot whose map point the handle does not know — one created after the last
+// Rebuild — is an error, never skipped: its votes would be missing.
+#ifndef SIVO_AMD_API_LOCALMAPADAPTER_H
+#define SIVO_AMD_API_LOCALMAPADAPTER_H
+
+#include <algorithm>
+#include <cstdint>
+#include <functional>
+#include <map>
+#include <set>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../../include/sivo_hip.h"
+
+namespace SIVO {
+namespace localmap_detail {
+
+inline void check(int rc, const char *what) {
+    if (rc == SIVO_ERR_INVALID_ARGUMENT) throw std::invalid_argument(std::string(what) + ": " + sivo_last_error());
+    if (rc != SIVO_OK) throw std::runtime_error(std::string(what) + ": " + sivo_last_error());
+}
+
+}  // namespace localmap_detail
+
+template <class KeyFrameT, class MapPointT>
+class LocalMapDevice {
+ public:
+    LocalMapDevice() {}
+    ~LocalMapDevice() {
+        if (mHandle) (void)sivo_localmap_destroy(mHandle);
+    }
+    LocalMapDevice(const LocalMapDevice &) = delete;
+    LocalMapDevice &operator=(const LocalMapDevice &) = delete;
+
+    // The tables of every keyframe of the map, in the vector's order (a keyframe's index is its position), and of every map point one of
+    // them holds.  A covisible, child, parent or observer outside the vector is an error.
+    void Rebuild(const std::vector<KeyFrameT *> &vpAllKFs) {
+        mvpKFs = vpAllKFs;
+        mKFIndex.clear(); mvpPoints.clear(); mPointIndex.clear();
+        const size_t K = mvpKFs.size();
+        for (size_t k = 0; k < K; ++k)
+            if (!mKFIndex.insert(std::make_pair(mvpKFs[k], (int32_t)k)).second) throw std::invalid_argument("LocalMapDevice::Rebuild: a keyframe is listed twice");
+        std::vector<int64_t> slotOff(1, 0), covisOff(1, 0), childOff(1, 0), obsOff(1, 0);
+        std::vector<int32_t> slotPoint, covisKf, childKf, parent(K, -1), obsKf, order(K);
+        std::vector<uint8_t> kfBad(K, 0), pointBad;
+        for (size_t k = 0; k < K; ++k) {
+            KeyFrameT *pKF = mvpKFs[k];
+            kfBad[k] = pKF->isBad() ? 1 : 0;
+            const std::vector<MapPointT *> vpMPs = pKF->GetMapPointMatches();
+            for (MapPointT *pMP : vpMPs) {
+                if (!pMP) { slotPoint.push_back(-1); continue; }
+                auto it = mPointIndex.find(pMP);
+                if (it == mPointIndex.end()) {
+                    it = mPointIndex.insert(std::make_pair(pMP, (int32_t)mvpPoints.size())).first;
+                    mvpPoints.push_back(pMP);
+                }
+                slotPoint.push_back(it->second);
+            }
+            slotOff.push_back((int64_t)slotPoint.size());
+            const std::vector<KeyFrameT *> vNeighs = pKF->GetVectorCovisibleKeyFrames();
+            for (size_t i = 0; i < vNeighs.size() && i < 10; ++i) covisKf.push_back(Known(vNeighs[i], "covisible"));   // (KeyFrame.cc:222-230)
+            covisOff.push_back((int64_t)covisKf.size());
+            const std::set<KeyFrameT *> spChilds = pKF->GetChildren();
+            for (KeyFrameT *pChild : spChilds) childKf.push_back(Known(pChild, "child"));
+            childOff.push_back((int64_t)childKf.size());
+            if (KeyFrameT *pParent = pKF->GetParent()) parent[k] = Known(pParent, "parent");
+            order[k] = (int32_t)k;
+        }
+        std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return std::less<KeyFrameT *>()(mvpKFs[(size_t)a], mvpKFs[(size_t)b]); });
+        for (MapPointT *pMP : mvpPoints) {
+            pointBad.push_back(pMP->isBad() ? 1 : 0);
+            const std::map<KeyFrameT *, size_t> observations = pMP->GetObservations();
+            for (auto mit = observations.begin(); mit != observations.end(); mit++) obsKf.push_back(Known(mit->first, "observer"));
+            obsOff.push_back((int64_t)obsKf.size());
+        }
+        SivoLocalMapTables t;
+        t.n_kf = (int32_t)K; t.n_points = (int32_t)mvpPoints.size();
+        t.obs_off = obsOff.data(); t.obs_kf = obsKf.data(); t.point_bad = pointBad.data(); t.kf_bad = kfBad.data();
+        t.slot_off = slotOff.data(); t.slot_point = slotPoint.data(); t.covis_off = covisOff.data(); t.covis_kf = covisKf.data();
+        t.child_off = childOff.data(); t.child_kf = childKf.data(); t.parent = parent.data(); t.kf_order = order.data();
+        if (mHandle) localmap_detail::check(sivo_localmap_replace(mHandle, &t), "LocalMapDevice::Rebuild");
+        else localmap_detail::check(sivo_localmap_create(&t, &mHandle), "LocalMapDevice::Rebuild");
+        mSlotOff.swap(slotOff);
+    }
+
+    void MarkBad(KeyFrameT *pKF) {
+        const int32_t k = Known(pKF, "keyframe to mark");
+        const uint8_t one = 1;
+        localmap_detail::check(sivo_localmap_set_bad(mHandle, 0, nullptr, nullptr, 1, &k, &one), "LocalMapDevice::MarkBad");
+    }
+    void MarkBad(MapPointT *pMP) {
+        const auto it = mPointIndex.find(pMP);
+        if (it == mPointIndex.end()) throw std::invalid_argument("LocalMapDevice::MarkBad: the map point was created after the last Rebuild");
+        const uint8_t one = 1;
+        localmap_detail::check(sivo_localmap_set_bad(mHandle, 1, &it->second, &one, 0, nullptr, nullptr), "LocalMapDevice::MarkBad");
+    }
+
+    // the index of a keyframe the last Rebuild listed
+    int32_t Known(KeyFrameT *pKF, const char *role) const {
+        const auto it = mKFIndex.find(pKF);
+        if (it == mKFIndex.end()) throw std::invalid_argument(std::string("LocalMapDevice: a ") + role + " is not among the keyframes of the last Rebuild");
+        return it->second;
+    }
+
+    sivo_localmap_t mHandle = nullptr;
+    std::vector<KeyFrameT *> mvpKFs;
+    std::map<KeyFrameT *, int32_t> mKFIndex;
+    std::vector<MapPointT *> mvpPoints;
+    std::map<MapPointT *, int32_t> mPointIndex;
+    std::vector<int64_t> mSlotOff;          // the slot counts: they bound the point list of a call
+};
+
+// In place of UpdateLocalKeyFrames(); UpdateLocalPoints(); (Tracking.cc:1092-1093).  Every keyframe and point of the handle is asked for
+// mnTrackReferenceForFrame == F.mnId, as the reference asks whatever it meets (:1114, :1198, :1213, :1223).
+template <class KeyFrameT, class MapPointT, class FrameT>
+void UpdateLocalMap(LocalMapDevice<KeyFrameT, MapPointT> &dev, FrameT &F, std::vector<KeyFrameT *> &vpLocalKeyFrames,
+                    std::vector<MapPointT *> &vpLocalMapPoints, KeyFrameT *&pReferenceKF) {
+    if (!dev.mHandle) throw std::invalid_argument("UpdateLocalMap: Rebuild has not run");
+    const size_t S = (size_t)F.numSemanticKeys;
+    std::vector<int32_t> framePoint(S, -1), kfMarked, pointMarked, prev;
+    for (size_t i = 0; i < S; ++i) {
+        MapPointT *pMP = F.mvpMapPoints[i];
+        if (!pMP) continue;
+        const auto it = dev.mPointIndex.find(pMP);
+        if (it == dev.mPointIndex.end())
+            throw std::runtime_error("UpdateLocalMap: frame slot " + std::to_string(i) + " holds a map point the device map does not know (created after the last Rebuild)");
+        framePoint[i] = it->second;
+    }
+    for (KeyFrameT *pKF : vpLocalKeyFrames) prev.push_back(dev.Known(pKF, "local keyframe"));
+    for (size_t k = 0; k < dev.mvpKFs.size(); ++k)
+        if (dev.mvpKFs[k]->mnTrackReferenceForFrame == F.mnId) kfMarked.push_back((int32_t)k);
+    for (size_t p = 0; p < dev.mvpPoints.size(); ++p)
+        if (dev.mvpPoints[p]->mnTrackReferenceForFrame == F.mnId) pointMarked.push_back((int32_t)p);
+    int64_t gPrev = 0;
+    for (int32_t k : prev) gPrev += dev.mSlotOff[(size_t)k + 1] - dev.mSlotOff[(size_t)k];
+    const size_t K = dev.mvpKFs.size();
+    const size_t pointCap = (size_t)std::min<int64_t>((int64_t)dev.mvpPoints.size(), std::max<int64_t>(dev.mSlotOff.back(), gPrev));
+    std::vector<int32_t> localKf(K), localPoint(pointCap);
+    std::vector<uint8_t> cleared(S, 0);
+    int32_t voted = 0, nLocalKf = 0, refKf = -1, nLocalPoints = 0;
+    localmap_detail::check(sivo_localmap_update(dev.mHandle, (int)S, framePoint.data(), (int)kfMarked.size(), kfMarked.data(), (int)pointMarked.size(),
+                                                pointMarked.data(), (int)prev.size(), prev.data(), &voted, cleared.data(), (int)K, localKf.data(),
+                                                &nLocalKf, &refKf, (int)pointCap, localPoint.data(), &nLocalPoints, nullptr),
+                           "UpdateLocalMap");
+    for (size_t i = 0; i < S; ++i)
+        if (cleared[i]) F.mvpMapPoints[i] = static_cast<MapPointT *>(nullptr);      // (:1139)
+    if (voted) {                                                                    // (:1144-1145: else the list stays)
+        vpLocalKeyFrames.clear();                                                   // (:1150)
+        for (int32_t j = 0; j < nLocalKf; ++j) {
+            KeyFrameT *pKF = dev.mvpKFs[(size_t)localKf[(size_t)j]];
+            vpLocalKeyFrames.push_back(pKF);
+            pKF->mnTrackReferenceForFrame = F.mnId;                                 // (:1171, :1200, :1215, :1225)
+        }
+        if (refKf >= 0) {                                                           // (:1231-1234)
+            pReferenceKF = dev.mvpKFs[(size_t)refKf];
+            F.mpReferenceKF = pReferenceKF;
+        }
+    }
+    vpLocalMapPoints.clear();                                                       // (:1097)
+    for (int32_t j = 0; j < nLocalPoints; ++j) {
+        MapPointT *pMP = dev.mvpPoints[(size_t)localPoint[(size_t)j]];
+        vpLocalMapPoints.push_back(pMP);                                            // (:1119)
+        pMP->mnTrackReferenceForFrame = F.mnId;                                     // (:1120)
+    }
+}
+
+}  // namespace SIVO
+
+#endif

@@ -1,0 +1,512 @@
+// localmap.hip — Tracking::UpdateLocalMap (reference src/orbslam/Tracking.cc:1087-1235) on a map that stays on the device: the tables of
+// SivoLocalMapTables are uploaded by sivo_localmap_create / _replace, sivo_localmap_set_bad scatters the isBad() flags that change in
+// between, and sivo_localmap_update runs one frame: one upload of the frame's lists, five launches, one download, one synchronisation.
+// The per-item bodies and the argument checks are localmap_math.hpp; everything is integer and no result depends on the order in which
+// atomics arrive (adds, ors, minima and maxima only).
+//
+// localmap_vote_kernel     ONE workgroup: the counting loop of :1129-1142 (cv_count_slot of covis_math.hpp, self = -1) into a histogram in
+//                          LDS, or into the zeroed counts in global memory above SIVO_COVIS_LDS_KF keyframes; writes slot_cleared.
+// localmap_select_kernel   ONE workgroup.  Stage 1 (:1156-1172): an order-preserving compaction over kf_order, a ballot per wave and a
+//                          prefix over the waves, the first strict maximum carried as one (count, position) key.  Stage 2 (:1177-1229)
+//                          is sequential: wave 0 walks the stage-1 keyframes, the ten covisibles on ten lanes, the children in chunks of
+//                          64 lanes, a ballot and its lowest set lane give "the first that is not bad and not marked"; every break is
+//                          the same in all lanes.  The marks (mnTrackReferenceForFrame == the frame's id) are a bitmap, in LDS up to
+//                          SIVO_COVIS_LDS_KF keyframes and in global memory above.  Then the whole workgroup writes the exclusive prefix
+//                          of the local keyframes' slot counts (list_off) and stamps the premarked points into first[].
+// localmap_first_kernel    pass 1 over the slot sequence g: atomicMin(first[p], g + 1).
+// localmap_count_kernel    pass 2a: how many slots of each block of 256 push their point.
+// localmap_scatter_kernel  pass 2b: exclusive scan inside the block, the sum of the blocks before it, the scatter in order.
+//
+// G and the list lengths stay on the device between the launches (hdr); the grids of the three point kernels are sized from a bound the
+// host knows: the handle's total slot count (the local list holds no keyframe twice), or the slot count of prev_local_kf where that is
+// larger.  first[] is part of the handle and is cleared by one memset at the head of every update, so no call sees an earlier one.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <stdexcept>
+#include <vector>
+
+#include "common.hpp"
+#include "solver_host.hpp"
+
+#include "localmap_math.hpp"
+
+namespace sivo {
+
+constexpr int LV_THREADS = 1024;
+constexpr int LS_THREADS = 1024;
+constexpr int LP_THREADS = 256;
+
+enum { LM_HDR_VOTED = 0, LM_HDR_N_KF, LM_HDR_REF, LM_HDR_N_POINTS, LM_HDR_N_LIST, LM_HDR_G, LM_HDR_WORDS = 8 };
+
+struct LmCall {
+    SivoLocalMapTables t;          // device pointers; kf_order is never null here
+    uint32_t *first;               // n_points, the handle's; LM_FIRST_NONE everywhere before the select kernel
+    int n_slots, n_kf_pre, n_pt_pre, n_prev, point_cap;
+    const int32_t *frame_point, *kf_pre, *pt_pre, *prev;
+    uint32_t *marks_g;             // one bit per keyframe, zeroed: the marks where n_kf > SIVO_COVIS_LDS_KF
+    int32_t *counts;               // n_kf, zeroed
+    int32_t *hdr;                  // LM_HDR_*
+    uint8_t *slot_cleared;         // n_slots
+    int32_t *local_kf;             // n_kf
+    int32_t *local_point;          // point_cap
+    int32_t *list_off;             // max(n_kf, n_prev) + 1
+    int32_t *block_sum;            // one per block of the point kernels
+};
+
+__global__ __launch_bounds__(LV_THREADS) void localmap_vote_kernel(LmCall a) {
+    __shared__ int32_t hist[SIVO_COVIS_LDS_KF];
+    const int tid = threadIdx.x, n_kf = a.t.n_kf;
+    const SivoObsTable o = lm_obs_table(a.t);
+    if (n_kf <= SIVO_COVIS_LDS_KF) {
+        for (int k = tid; k < n_kf; k += LV_THREADS) hist[k] = 0;
+        __syncthreads();
+        for (int i = tid; i < a.n_slots; i += LV_THREADS) {
+            const int32_t p = a.frame_point[i];
+            a.slot_cleared[i] = lm_slot_cleared(a.t, p);
+            cv_count_slot(o, p, -1, [&](int32_t k) { atomicAdd(&hist[k], 1); });
+        }
+        __syncthreads();
+        for (int k = tid; k < n_kf; k += LV_THREADS) a.counts[k] = hist[k];
+    } else {
+        for (int i = tid; i < a.n_slots; i += LV_THREADS) {
+            const int32_t p = a.frame_point[i];
+            a.slot_cleared[i] = lm_slot_cleared(a.t, p);
+            cv_count_slot(o, p, -1, [&](int32_t k) { atomicAdd(&a.counts[k], 1); });
+        }
+    }
+}
+
+// The exclusive prefix of v over the workgroup and its total; wave_tot holds one entry per wave.  Every thread of the workgroup calls it.
+template <int THREADS>
+__device__ inline int32_t lm_block_excl_scan(int32_t v, int32_t *wave_tot, int32_t &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int32_t u = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += u;
+    }
+    if (lane == 63) wave_tot[wave] = inc;
+    __syncthreads();
+    int32_t before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; ++w) {
+        const int32_t x = wave_tot[w];
+        if (w < wave) before += x;
+        total += x;
+    }
+    __syncthreads();
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(LS_THREADS) void localmap_select_kernel(LmCall a) {
+    __shared__ uint32_t marks_l[SIVO_COVIS_LDS_KF / 32];
+    __shared__ int32_t wave_tot[LS_THREADS / 64];
+    __shared__ unsigned long long best;
+    __shared__ int32_t s_any, s_n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_kf = a.t.n_kf;
+    const bool lds_marks = n_kf <= SIVO_COVIS_LDS_KF;
+    uint32_t *marks = lds_marks ? marks_l : a.marks_g;
+    if (lds_marks)
+        for (int w = tid; w < (n_kf + 31) / 32; w += LS_THREADS) marks_l[w] = 0;
+    if (tid == 0) { best = 0; s_any = 0; s_n = 0; }
+    __syncthreads();
+    for (int i = tid; i < a.n_kf_pre; i += LS_THREADS) atomicOr(&marks[a.kf_pre[i] >> 5], lm_mark_bit(a.kf_pre[i]));
+    for (int i = tid; i < a.n_pt_pre; i += LS_THREADS) a.first[a.pt_pre[i]] = LM_FIRST_PREMARKED;
+    int any = 0;
+    for (int k = tid; k < n_kf; k += LS_THREADS) any |= a.counts[k] > 0;
+    if (any) s_any = 1;
+    __syncthreads();
+    const bool voted = s_any != 0;                                      // (:1144)
+
+    // ---- stage 1 (:1156-1172): the voted keyframes that are not bad, in kf_order; n is the same in every thread
+    int32_t n = 0;
+    if (voted) {
+        unsigned long long my_best = 0;
+        for (int base = 0; base < n_kf; base += LS_THREADS) {
+            const int i = base + tid;
+            int32_t k = -1;
+            bool take = false;
+            if (i < n_kf) {
+                k = a.t.kf_order[i];
+                take = lm_stage1_takes(a.t, a.counts, k);
+            }
+            const unsigned long long b = __ballot(take);
+            const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
+            if (lane == 0) wave_tot[wave] = __popcll(b);
+            __syncthreads();
+            int32_t before = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < LS_THREADS / 64; ++w) {
+                const int32_t x = wave_tot[w];
+                if (w < wave) before += x;
+                total += x;
+            }
+            if (take) {
+                a.local_kf[n + before + in_wave] = k;                   // (:1170)
+                atomicOr(&marks[k >> 5], lm_mark_bit(k));               // (:1171)
+                const unsigned long long key = lm_max_key(a.counts[k], i);
+                if (key > my_best) my_best = key;                       // (:1165-1168)
+            }
+            n += total;
+            __syncthreads();
+        }
+        if (my_best) atomicMax(&best, my_best);
+    }
+    __syncthreads();
+
+    // ---- stage 2 (:1177-1229): wave 0, every lane on the same path
+    if (wave == 0 && voted) {
+        const int32_t n1 = n;                                           // itEndKF is taken before the loop
+        int32_t m = n;
+        auto push = [&](int32_t k) {
+            if (lane == 0) a.local_kf[m] = k;
+            marks[k >> 5] |= lm_mark_bit(k);                            // the same store in every lane: each lane reads its own later
+            ++m;
+        };
+        for (int32_t j = 0; j < n1; ++j) {
+            if (m > LM_MAX_LOCAL) break;                                // (:1183)
+            const int32_t k = a.local_kf[j];
+            {
+                const int64_t c0 = a.t.covis_off[k];
+                const int cn = (int)min((long long)(a.t.covis_off[k + 1] - c0), (long long)LM_BEST_COVIS);     // (:1189)
+                int32_t c = -1;
+                bool ok = false;
+                if (lane < cn) {
+                    c = a.t.covis_kf[c0 + lane];
+                    ok = lm_neighbour_ok(a.t, marks, c);
+                }
+                const unsigned long long b = __ballot(ok);
+                if (b) push(__shfl(c, __ffsll(b) - 1, 64));             // (:1197-1201)
+            }
+            for (int64_t cb = a.t.child_off[k], c1 = a.t.child_off[k + 1]; cb < c1; cb += 64) {
+                int32_t c = -1;
+                bool ok = false;
+                if (cb + lane < c1) {
+                    c = a.t.child_kf[cb + lane];
+                    ok = lm_neighbour_ok(a.t, marks, c);
+                }
+                const unsigned long long b = __ballot(ok);
+                if (b) {
+                    push(__shfl(c, __ffsll(b) - 1, 64));                // (:1212-1216)
+                    break;
+                }
+            }
+            const int32_t par = a.t.parent[k];
+            if (par >= 0 && !lm_marked(marks, par)) {                   // (:1222-1223: isBad() is not asked)
+                push(par);
+                break;                                                  // (:1226: leaves the loop over the keyframes)
+            }
+        }
+        if (lane == 0) s_n = m;
+    }
+    __syncthreads();
+
+    // ---- what the point passes walk: the new list, or the caller's where nobody voted (:1144-1145, then :1093)
+    const int32_t n_list = voted ? s_n : a.n_prev;
+    const int32_t *list = voted ? a.local_kf : a.prev;
+    int32_t run = 0;
+    for (int base = 0; base < n_list; base += LS_THREADS) {
+        const int i = base + tid;
+        int32_t cnt = 0;
+        if (i < n_list) cnt = (int32_t)(a.t.slot_off[list[i] + 1] - a.t.slot_off[list[i]]);
+        int32_t total;
+        const int32_t excl = lm_block_excl_scan<LS_THREADS>(cnt, wave_tot, total);
+        if (i < n_list) a.list_off[i] = run + excl;
+        run += total;
+    }
+    if (tid == 0) {
+        a.list_off[n_list] = run;
+        a.hdr[LM_HDR_VOTED] = voted;
+        a.hdr[LM_HDR_N_KF] = voted ? s_n : 0;
+        a.hdr[LM_HDR_REF] = best ? a.t.kf_order[lm_key_pos(best)] : -1;  // (:1231)
+        a.hdr[LM_HDR_N_LIST] = n_list;
+        a.hdr[LM_HDR_G] = run;
+    }
+}
+
+struct LmList {
+    const int32_t *list;
+    int32_t n, G;
+};
+
+__device__ inline LmList lm_list(const LmCall &a) {
+    LmList l;
+    l.list = a.hdr[LM_HDR_VOTED] ? a.local_kf : a.prev;
+    l.n = a.hdr[LM_HDR_N_LIST];
+    l.G = a.hdr[LM_HDR_G];
+    return l;
+}
+
+__global__ __launch_bounds__(LP_THREADS) void localmap_first_kernel(LmCall a) {
+    const LmList l = lm_list(a);
+    const int64_t g = (int64_t)blockIdx.x * LP_THREADS + threadIdx.x;
+    if (g >= l.G) return;
+    const int32_t p = lm_slot_point(a.t, l.list, a.list_off, l.n, (int32_t)g);
+    if (p >= 0) atomicMin(&a.first[p], (uint32_t)g + 1u);
+}
+
+__global__ __launch_bounds__(LP_THREADS) void localmap_count_kernel(LmCall a) {
+    __shared__ int32_t wave_n[LP_THREADS / 64];
+    const LmList l = lm_list(a);
+    const int64_t g = (int64_t)blockIdx.x * LP_THREADS + threadIdx.x;
+    if ((int64_t)blockIdx.x * LP_THREADS >= l.G) return;               // the whole block
+    bool keep = false;
+    if (g < l.G) keep = lm_point_survives(a.t, a.first, lm_slot_point(a.t, l.list, a.list_off, l.n, (int32_t)g), (int32_t)g);
+    const unsigned long long b = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = __popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t s = 0;
+#pragma unroll
+        for (int w = 0; w < LP_THREADS / 64; ++w) s += wave_n[w];
+        a.block_sum[blockIdx.x] = s;
+    }
+}
+
+// x[0] + .. + x[n - 1], the same in every thread of the workgroup
+__device__ inline int32_t lm_block_sum(const int32_t *x, int n, int32_t *acc) {
+    if (threadIdx.x == 0) *acc = 0;
+    __syncthreads();
+    int32_t s = 0;
+    for (int i = threadIdx.x; i < n; i += LP_THREADS) s += x[i];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(acc, s);
+    __syncthreads();
+    const int32_t r = *acc;
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(LP_THREADS) void localmap_scatter_kernel(LmCall a) {
+    __shared__ int32_t wave_tot[LP_THREADS / 64];
+    __shared__ int32_t acc;
+    const LmList l = lm_list(a);
+    const int nb = (int)(((int64_t)l.G + LP_THREADS - 1) / LP_THREADS);
+    const int blk = blockIdx.x;
+    if (blk >= nb && blk != 0) return;                                  // the whole block; block 0 stays for the count
+    const int64_t g = (int64_t)blk * LP_THREADS + threadIdx.x;
+    int32_t p = -1;
+    bool keep = false;
+    if (g < l.G) {
+        p = lm_slot_point(a.t, l.list, a.list_off, l.n, (int32_t)g);
+        keep = lm_point_survives(a.t, a.first, p, (int32_t)g);
+    }
+    int32_t total;
+    const int32_t excl = lm_block_excl_scan<LP_THREADS>(keep ? 1 : 0, wave_tot, total);
+    const int32_t base = lm_block_sum(a.block_sum, blk, &acc);
+    if (keep && base + excl < a.point_cap) a.local_point[base + excl] = p;     // (:1119)
+    if (blk == 0) {
+        const int32_t all = lm_block_sum(a.block_sum, nb, &acc);
+        if (threadIdx.x == 0) a.hdr[LM_HDR_N_POINTS] = all;
+    }
+}
+
+struct LmBadArgs {
+    uint8_t *point_bad, *kf_bad;
+    int n_points, n_kf;
+    const int32_t *point_idx, *kf_idx;
+    const uint8_t *point_val, *kf_val;
+};
+
+__global__ __launch_bounds__(LP_THREADS) void localmap_set_bad_kernel(LmBadArgs a) {
+    const int i = blockIdx.x * LP_THREADS + (int)threadIdx.x;
+    if (i < a.n_points) a.point_bad[a.point_idx[i]] = a.point_val[i];
+    else if (i - a.n_points < a.n_kf) a.kf_bad[a.kf_idx[i - a.n_points]] = a.kf_val[i - a.n_points];
+}
+
+static void lm_throw(const char *what, const char *e) {
+    if (e) throw std::invalid_argument(std::string(what) + ": " + e);
+}
+
+static SolverCtx &lm_ctx() {
+    static thread_local SolverCtx c(false, 1 << 20, 0, 1 << 20);
+    c.bind();
+    return c;
+}
+
+}  // namespace sivo
+
+using namespace sivo;
+
+struct sivo_localmap {
+    std::mutex mu;
+    int device = -1;
+    DeviceBuf dev{1 << 20};                // the tables and first[], grow-only
+    SivoLocalMapTables d{};                // device pointers
+    uint32_t *first = nullptr;
+    std::vector<int64_t> slot_off;         // host copy: the slot counts bound the grids and size prev_local_kf's walk
+    int64_t total_slots = 0;
+};
+
+// the checked tables into the handle's buffer: one copy, synchronised before it returns
+static void lm_load(sivo_localmap *m, const SivoLocalMapTables &t) {
+    const size_t K = (size_t)t.n_kf, P = (size_t)t.n_points;
+    const size_t no = P ? (size_t)t.obs_off[P] : 0, ns = K ? (size_t)t.slot_off[K] : 0, nc = K ? (size_t)t.covis_off[K] : 0,
+                 nh = K ? (size_t)t.child_off[K] : 0;
+    std::vector<int32_t> identity;
+    if (!t.kf_order) {
+        identity.resize(K);
+        for (size_t k = 0; k < K; ++k) identity[k] = (int32_t)k;
+    }
+    SolverCtx &c = lm_ctx();
+    SivoLocalMapTables d{};
+    uint32_t *first = nullptr;
+    Layout L;
+    d.n_kf = t.n_kf; d.n_points = t.n_points;
+    L.copy(d.obs_off, t.obs_off, P ? 8 * (P + 1) : 0); L.copy(d.obs_kf, t.obs_kf, 4 * no); L.copy(d.point_bad, t.point_bad, P);
+    L.copy(d.kf_bad, t.kf_bad, K); L.copy(d.slot_off, t.slot_off, K ? 8 * (K + 1) : 0); L.copy(d.slot_point, t.slot_point, 4 * ns);
+    L.copy(d.covis_off, t.covis_off, K ? 8 * (K + 1) : 0); L.copy(d.covis_kf, t.covis_kf, 4 * nc);
+    L.copy(d.child_off, t.child_off, K ? 8 * (K + 1) : 0); L.copy(d.child_kf, t.child_kf, 4 * nh); L.copy(d.parent, t.parent, 4 * K);
+    L.copy(d.kf_order, t.kf_order ? t.kf_order : identity.data(), 4 * K);
+    L.take(first, 4 * P);
+    std::vector<char> host(L.staged());
+    L.place(m->dev.reserve(L.bytes()), host.data());
+    L.send(c.stream);
+    SIVO_HIP(hipStreamSynchronize(c.stream));
+    m->d = d;
+    m->first = first;
+    m->slot_off.assign(K + 1, 0);
+    if (K) std::memcpy(m->slot_off.data(), t.slot_off, 8 * (K + 1));
+    m->total_slots = (int64_t)ns;
+}
+
+extern "C" int sivo_localmap_create(const SivoLocalMapTables *t, sivo_localmap_t *map) {
+    return guarded([&] {
+        if (!map) throw std::invalid_argument("sivo_localmap_create: null handle pointer");
+        *map = nullptr;
+        lm_throw("sivo_localmap_create", lm_check_tables(t));
+        require_device();
+        sivo_localmap *m = new sivo_localmap;
+        try {
+            SIVO_HIP(hipGetDevice(&m->device));
+            lm_load(m, *t);
+        } catch (...) {
+            delete m;
+            throw;
+        }
+        *map = m;
+        return SIVO_OK;
+    });
+}
+
+extern "C" int sivo_localmap_replace(sivo_localmap_t m, const SivoLocalMapTables *t) {
+    return guarded([&] {
+        if (!m) throw std::invalid_argument("sivo_localmap_replace: null handle");
+        lm_throw("sivo_localmap_replace", lm_check_tables(t));
+        std::lock_guard<std::mutex> lock(m->mu);
+        DeviceGuard dg(m->device);
+        lm_load(m, *t);
+        return SIVO_OK;
+    });
+}
+
+extern "C" int sivo_localmap_destroy(sivo_localmap_t m) {
+    return guarded([&] {
+        if (!m) return SIVO_OK;
+        {
+            DeviceGuard dg(m->device);
+            m->dev.release();
+        }
+        delete m;
+        return SIVO_OK;
+    });
+}
+
+extern "C" int sivo_localmap_set_bad(sivo_localmap_t m, int n_points, const int32_t *point_idx, const uint8_t *point_val, int n_kf,
+                                     const int32_t *kf_idx, const uint8_t *kf_val) {
+    return guarded([&] {
+        if (!m) throw std::invalid_argument("sivo_localmap_set_bad: null handle");
+        std::lock_guard<std::mutex> lock(m->mu);
+        lm_throw("sivo_localmap_set_bad", lm_check_set_bad(m->d.n_kf, m->d.n_points, n_points, point_idx, point_val, n_kf, kf_idx, kf_val));
+        if (n_points == 0 && n_kf == 0) return SIVO_OK;
+        // of an index listed twice the later entry holds: the scatter sees every index once
+        std::map<int32_t, uint8_t> pm, km;
+        for (int i = 0; i < n_points; ++i) pm[point_idx[i]] = point_val[i] ? 1 : 0;
+        for (int i = 0; i < n_kf; ++i) km[kf_idx[i]] = kf_val[i] ? 1 : 0;
+        std::vector<int32_t> pi, ki;
+        std::vector<uint8_t> pv, kv;
+        for (const auto &e : pm) { pi.push_back(e.first); pv.push_back(e.second); }
+        for (const auto &e : km) { ki.push_back(e.first); kv.push_back(e.second); }
+        DeviceGuard dg(m->device);
+        SolverCtx &c = lm_ctx();
+        LmBadArgs a;
+        Layout L;
+        L.copy(a.point_idx, pi.data(), 4 * pi.size()); L.copy(a.point_val, pv.data(), pv.size());
+        L.copy(a.kf_idx, ki.data(), 4 * ki.size()); L.copy(a.kf_val, kv.data(), kv.size());
+        L.place(c.dev.reserve(L.bytes()), c.in.reserve(L.bytes()));
+        a.point_bad = const_cast<uint8_t *>(m->d.point_bad); a.kf_bad = const_cast<uint8_t *>(m->d.kf_bad);
+        a.n_points = (int)pi.size(); a.n_kf = (int)ki.size();
+        L.send(c.stream);
+        hipLaunchKernelGGL(localmap_set_bad_kernel, dim3((unsigned)cdiv(a.n_points + a.n_kf, LP_THREADS)), dim3(LP_THREADS), 0, c.stream, a);
+        SIVO_HIP(hipGetLastError());
+        SIVO_HIP(hipStreamSynchronize(c.stream));
+        return SIVO_OK;
+    });
+}
+
+extern "C" int sivo_localmap_update(sivo_localmap_t m, int n_slots, const int32_t *frame_point, int n_kf_premarked,
+                                    const int32_t *kf_premarked, int n_point_premarked, const int32_t *point_premarked, int n_prev,
+                                    const int32_t *prev_local_kf, int32_t *voted, uint8_t *slot_cleared, int kf_capacity,
+                                    int32_t *local_kf, int32_t *n_local_kf, int32_t *ref_kf, int point_capacity, int32_t *local_point,
+                                    int32_t *n_local_points, int32_t *counts) {
+    return guarded([&] {
+        if (!m) throw std::invalid_argument("sivo_localmap_update: null handle");
+        std::lock_guard<std::mutex> lock(m->mu);
+        int64_t g_prev = 0;
+        lm_throw("sivo_localmap_update",
+                 lm_check_update(m->d.n_kf, m->d.n_points, m->slot_off.data(), n_slots, frame_point, n_kf_premarked, kf_premarked, n_point_premarked,
+                                 point_premarked, n_prev, prev_local_kf, voted, slot_cleared, kf_capacity, local_kf, n_local_kf, ref_kf,
+                                 point_capacity, local_point, n_local_points, &g_prev));
+        require_device();
+        DeviceGuard dg(m->device);
+        SolverCtx &c = lm_ctx();
+        const size_t K = (size_t)m->d.n_kf, P = (size_t)m->d.n_points, S = (size_t)n_slots;
+        const int64_t g_max = std::max(m->total_slots, g_prev);         // no list the point passes walk holds more slots
+        const unsigned nb = (unsigned)std::max<int64_t>(1, cdiv64(g_max, LP_THREADS));
+        LmCall a;
+        a.t = m->d; a.first = m->first;
+        a.n_slots = n_slots; a.n_kf_pre = n_kf_premarked; a.n_pt_pre = n_point_premarked; a.n_prev = n_prev;
+        a.point_cap = (int)std::min<int64_t>(point_capacity, std::min<int64_t>((int64_t)P, g_max));
+        Layout L;
+        L.copy(a.frame_point, frame_point, 4 * S); L.copy(a.kf_pre, kf_premarked, 4 * (size_t)n_kf_premarked);
+        L.copy(a.pt_pre, point_premarked, 4 * (size_t)n_point_premarked); L.copy(a.prev, prev_local_kf, 4 * (size_t)n_prev);
+        L.zero(a.marks_g, K > SIVO_COVIS_LDS_KF ? 4 * ((K + 31) / 32) : 0); L.zero(a.counts, 4 * K);
+        L.take(a.hdr, 4 * LM_HDR_WORDS); L.take(a.slot_cleared, S); L.take(a.local_kf, 4 * K); L.take(a.local_point, 4 * (size_t)a.point_cap);
+        L.take(a.list_off, 4 * (std::max(K, (size_t)n_prev) + 1)); L.take(a.block_sum, 4 * (size_t)nb);       // scratch: not copied back
+        L.place(c.dev.reserve(L.bytes()), c.in.reserve(L.bytes()));
+        L.send(c.stream);
+        if (P) SIVO_HIP(hipMemsetAsync(m->first, 0xFF, 4 * P, c.stream));
+        hipLaunchKernelGGL(localmap_vote_kernel, dim3(1), dim3(LV_THREADS), 0, c.stream, a);
+        hipLaunchKernelGGL(localmap_select_kernel, dim3(1), dim3(LS_THREADS), 0, c.stream, a);
+        hipLaunchKernelGGL(localmap_first_kernel, dim3(nb), dim3(LP_THREADS), 0, c.stream, a);
+        hipLaunchKernelGGL(localmap_count_kernel, dim3(nb), dim3(LP_THREADS), 0, c.stream, a);
+        hipLaunchKernelGGL(localmap_scatter_kernel, dim3(nb), dim3(LP_THREADS), 0, c.stream, a);
+        SIVO_HIP(hipGetLastError());
+        const size_t down = (size_t)((const char *)a.local_point - (const char *)a.counts) + 4 * (size_t)a.point_cap;
+        SIVO_HIP(hipMemcpyAsync(L.host(a.counts), a.counts, down, hipMemcpyDeviceToHost, c.stream));
+        SIVO_HIP(hipStreamSynchronize(c.stream));
+        const int32_t *hdr = L.host(a.hdr);
+        const int32_t v = hdr[LM_HDR_VOTED], nk = hdr[LM_HDR_N_KF], np = hdr[LM_HDR_N_POINTS];
+        if (v && nk > kf_capacity) return fail(SIVO_ERR_CAPACITY, "sivo_localmap_update: %d local keyframes, capacity %d", nk, kf_capacity);
+        if (np > point_capacity) return fail(SIVO_ERR_CAPACITY, "sivo_localmap_update: %d local map points, capacity %d", np, point_capacity);
+        *voted = v;
+        if (S) std::memcpy(slot_cleared, L.host(a.slot_cleared), S);
+        if (v) {
+            *n_local_kf = nk;
+            if (nk) std::memcpy(local_kf, L.host(a.local_kf), 4 * (size_t)nk);
+        }
+        *ref_kf = hdr[LM_HDR_REF];
+        *n_local_points = np;
+        if (np) std::memcpy(local_point, L.host(a.local_point), 4 * (size_t)np);
+        if (counts && K) std::memcpy(counts, L.host(a.counts), 4 * K);
+        return SIVO_OK;
+    });
+}

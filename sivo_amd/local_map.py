@@ -1,0 +1,116 @@
+"""The tracking thread's local map on a map that stays on the device: Tracking::UpdateLocalMap (reference src/orbslam/Tracking.cc:1087-1235)
+— the vote, mvpLocalKeyFrames, mpReferenceKF and mvpLocalMapPoints — per frame, on tables uploaded once (sivo_amd/csrc/localmap.hip).
+Host numpy arrays in and out.  Integer results: exact, in the reference's order."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, lib
+
+LDS_KF = 8192                                                                              # SIVO_COVIS_LDS_KF
+TABLE_FIELDS = ("obs_off", "obs_kf", "point_bad", "kf_bad", "slot_off", "slot_point", "covis_off", "covis_kf", "child_off", "child_kf",
+                "parent", "kf_order")
+_DTYPE = dict(obs_off=np.int64, obs_kf=np.int32, point_bad=np.uint8, kf_bad=np.uint8, slot_off=np.int64, slot_point=np.int32,
+              covis_off=np.int64, covis_kf=np.int32, child_off=np.int64, child_kf=np.int32, parent=np.int32, kf_order=np.int32)
+
+
+class _Tables(C.Structure):  # == SivoLocalMapTables
+    _fields_ = [("n_kf", C.c_int32), ("n_points", C.c_int32)] + [(f, C.c_void_p) for f in TABLE_FIELDS]
+
+
+def _a(x, dt):
+    return np.ascontiguousarray(x, dt).ravel()
+
+
+def _p(x):
+    return x.ctypes.data if x is not None and x.size else None
+
+
+class Result:
+    """What one update leaves: voted (False: keyframeCounter was empty, local_kf is None and the points are those of prev_local_kf),
+    slot_cleared (one byte per frame slot), local_kf, ref_kf (-1: mpReferenceKF stays), local_points, counts (the vote, per keyframe)."""
+
+    def __init__(self, voted, slot_cleared, local_kf, ref_kf, local_points, counts):
+        self.voted, self.slot_cleared, self.local_kf, self.ref_kf = voted, slot_cleared, local_kf, ref_kf
+        self.local_points, self.counts = local_points, counts
+
+
+class LocalMap:
+    """The map as arrays over dense keyframe and point indices (SivoLocalMapTables of include/sivo_hip.h): obs_off / obs_kf (CSR point ->
+    observing keyframes), point_bad, kf_bad, slot_off / slot_point (CSR keyframe -> GetMapPointMatches(), -1 for null), covis_off /
+    covis_kf (mvpOrderedConnectedKeyFrames), child_off / child_kf (mspChildren in the set's order), parent (-1: none) and kf_order (the
+    keyframes in pointer order; None: 0, 1, 2 ...).  The arrays are uploaded here and stay on the device until replace() or close()."""
+
+    def __init__(self, n_kf, **tables):
+        self._h = C.c_void_p()
+        st = self._struct(n_kf, tables)
+        check(lib().sivo_localmap_create(C.byref(st), C.byref(self._h)))
+
+    def _struct(self, n_kf, tables):
+        unknown = set(tables) - set(TABLE_FIELDS)
+        if unknown:
+            raise TypeError("unknown table " + ", ".join(sorted(unknown)))
+        t = {f: None if tables.get(f) is None else _a(tables[f], _DTYPE[f]) for f in TABLE_FIELDS}
+        n_points = 0 if t["point_bad"] is None else len(t["point_bad"])
+        self._keep = t                                                 # alive over the call
+        self.n_kf, self.n_points = int(n_kf), n_points
+        off = t["slot_off"]
+        self._slot_off = np.zeros(self.n_kf + 1, np.int64) if off is None or len(off) != self.n_kf + 1 else off.copy()
+        return _Tables(self.n_kf, n_points, *[_p(t[f]) for f in TABLE_FIELDS])
+
+    def replace(self, n_kf, **tables):
+        """A new set of tables into the same handle."""
+        st = self._struct(n_kf, tables)
+        check(lib().sivo_localmap_replace(self._h, C.byref(st)))
+
+    def set_bad(self, points=(), point_values=(), kfs=(), kf_values=()):
+        """isBad() of the listed points / keyframes becomes the listed value."""
+        pi, pv, ki, kv = _a(points, np.int32), _a(point_values, np.uint8), _a(kfs, np.int32), _a(kf_values, np.uint8)
+        if len(pi) != len(pv) or len(ki) != len(kv):
+            raise ValueError("one value per index")
+        check(lib().sivo_localmap_set_bad(self._h, len(pi), _p(pi), _p(pv), len(ki), _p(ki), _p(kv)))
+
+    def update(self, frame_point, kf_premarked=None, point_premarked=None, prev_local_kf=(), *, kf_capacity=None, point_capacity=None, out=None):
+        """One frame.  frame_point: mCurrentFrame.mvpMapPoints as point indices, -1 for null; kf_premarked / point_premarked: the indices
+        whose mnTrackReferenceForFrame already equals the frame's id; prev_local_kf: the local keyframes the caller holds.  The capacities
+        default to what no result can exceed.  `out` (slot_cleared, local_kf, local_point, counts: arrays of the capacities' sizes) lets
+        a caller see which entries the call wrote."""
+        fp = _a(frame_point, np.int32)
+        kp = _a(() if kf_premarked is None else kf_premarked, np.int32)
+        pp = _a(() if point_premarked is None else point_premarked, np.int32)
+        prev = _a(prev_local_kf, np.int32)
+        in_range = prev[(prev >= 0) & (prev < self.n_kf)]              # (the library reports the others)
+        g_max = max(int(self._slot_off[-1]), int((self._slot_off[in_range + 1] - self._slot_off[in_range]).sum()))
+        kcap = self.n_kf if kf_capacity is None else int(kf_capacity)
+        pcap = min(self.n_points, g_max) if point_capacity is None else int(point_capacity)
+        out = out or {}
+        cleared = out.get("slot_cleared", np.zeros(len(fp), np.uint8))
+        local_kf = out.get("local_kf", np.zeros(kcap, np.int32))
+        local_point = out.get("local_point", np.zeros(pcap, np.int32))
+        counts = out.get("counts", np.zeros(self.n_kf, np.int32))
+        for name, arr, n, dt in (("slot_cleared", cleared, len(fp), np.uint8), ("local_kf", local_kf, kcap, np.int32),
+                                 ("local_point", local_point, pcap, np.int32), ("counts", counts, self.n_kf, np.int32)):
+            if arr.dtype != dt or arr.ndim != 1 or len(arr) < n or not arr.flags.c_contiguous:
+                raise ValueError("out[%r] must be a contiguous %s array of at least %d entries" % (name, np.dtype(dt).name, n))
+        voted, n_kf, ref, n_pts = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        check(lib().sivo_localmap_update(self._h, len(fp), _p(fp), len(kp), _p(kp), len(pp), _p(pp), len(prev), _p(prev), C.byref(voted),
+                                         _p(cleared), kcap, _p(local_kf), C.byref(n_kf), C.byref(ref), pcap, _p(local_point), C.byref(n_pts),
+                                         _p(counts)))
+        return Result(bool(voted.value), cleared, local_kf[:n_kf.value] if voted.value else None, int(ref.value), local_point[:n_pts.value], counts)
+
+    def close(self):
+        if self._h:
+            check(lib().sivo_localmap_destroy(self._h))
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
