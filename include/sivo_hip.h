@@ -1173,6 +1173,99 @@ int sivo_bowdb_size(sivo_bowdb_t db, int32_t *n_slots);
 int sivo_bowdb_query(sivo_bowdb_t db, const int32_t *q_words, const double *q_values, int nq, int32_t *common,
                      int32_t *first_word, double *score, int32_t *n_slots);
 
+/* ===========================================================================
+ * The two map corrections of the loop closer: LoopClosing::CorrectLoop's pose
+ * propagation and point correction (reference src/orbslam/LoopClosing.cc:436-526)
+ * and the map update behind the global bundle adjustment (LoopClosing.cc:694-753).
+ * Sim3 arithmetic in double in Eigen's operation order, cv::Mat arithmetic in float
+ * under OpenCV's gemm rules, the reference's sequential effects reproduced: equal to
+ * the reference's loops bit for bit.  Every NaN leaves as 0x7FC00000 (float) or
+ * 0x7FF8000000000000 (double).  DESIGN 3.6j.
+ * For both calls: a negative count, a NULL array with a non-zero count, an offset
+ * array that does not start at 0 or that decreases, an index outside its table, or
+ * one of the conditions named below -> SIVO_ERR_INVALID_ARGUMENT with a message of
+ * its own, before any device is touched.
+ * ======================================================================== */
+typedef struct {
+    int32_t n_kf;              /* >= 1: the keyframes of CorrectedSim3 in the order that std::map iterates (by pointer) */
+    int32_t cur;               /* index of mpCurrentKF among them */
+    int32_t n_all;             /* >= n_kf: the keyframe table; entries n_kf .. are observers / reference keyframes only */
+    int32_t n_points;
+    const float *tiw;          /* 16 n_kf: GetPose(), row-major */
+    const float *twc_cur;      /* 16: mpCurrentKF->GetPoseInverse() */
+    const double *scw;         /* 8: mg2oScw as qx qy qz qw tx ty tz s; s > 0 */
+    const float *ow;           /* 3 n_all: GetCameraCenter() */
+    const int64_t *slot_off;   /* n_kf + 1, CSR over GetMapPointMatches() of each corrected keyframe */
+    const int32_t *slot_point; /* a point index, -1 for a null slot */
+    const float *pos;          /* 3 n_points: GetWorldPos() */
+    const uint8_t *skip;       /* n_points: isBad() || mnCorrectedByKF == mpCurrentKF->mnId on entry */
+    const int64_t *obs_off;    /* n_points + 1, CSR over mObservations in its order, all observations (as sivo_mappoint_refresh) */
+    const int32_t *obs_kf;     /* indices into the keyframe table */
+    const int32_t *ref_kf;     /* n_points: mpRefKF in the table; -1 only for a point that no slot would move */
+    const float *level_scale;  /* n_points, as sivo_mappoint_refresh */
+    const float *last_scale;
+    double *noncorrected_siw;  /* out, 8 n_kf: NonCorrectedSim3 */
+    double *corrected_siw;     /* out, 8 n_kf: CorrectedSim3 */
+    float *tiw_out;            /* out, 16 n_kf: the pose SetPose receives, [R t/s; 0 0 0 1] */
+    float *ow_out;             /* out, 3 n_kf: the camera centre after that SetPose */
+    int32_t *corrected_by;     /* out, n_points: the keyframe that moved the point (mnCorrectedReference), -1: untouched */
+    float *pos_out;            /* out, 3 n_points     } written for the moved points only; normal and the distances */
+    float *normal;             /* out, 3 n_points     } only where flags comes back 0 */
+    float *max_dist;           /* out, n_points       } */
+    float *min_dist;           /* out, n_points       } */
+    uint8_t *flags;            /* out, n_points: 0 or SIVO_MP_NO_OBSERVATION } */
+} SivoLoopCorrect;
+
+/* LoopClosing.cc:447-526 on arrays.  Keyframe i: NonCorrected = Sim3(Quaterniond(Riw), tiw, 1), the quaternion not
+ * normalised; Corrected = Sim3(Ric, tic, 1) * Scw with Tic = Tiw * Twc one float gemm, scw verbatim for i == cur; the
+ * new pose is [toRotationMatrix(q) t * (1 / s)] narrowed to float, its camera centre KeyFrame::SetPose's.  A point is
+ * moved by the first keyframe of the given order that holds it in a slot, once: pos_out = (float)
+ * CorrectedSwi.map(Siw.map((double)pos)).  UpdateNormalAndDepth runs at that moment: keyframe i's SetPose follows its
+ * point loop, so for a point moved by keyframe i the camera centre of keyframe k is ow_out[k] where k < n_kf and
+ * k < i, else ow[k].  Also refused: cur outside [0, n_kf), scw[7] <= 0 or NaN, ref_kf < 0 for a point that would be
+ * moved. */
+int sivo_loop_correct(const SivoLoopCorrect *problem);
+
+enum {
+    SIVO_GBA_POINT_BAD = 0,         /* LoopClosing.cc:726 */
+    SIVO_GBA_POINT_FROM_BA = 1,     /* :729-731, pos_out = pos_gba */
+    SIVO_GBA_POINT_CARRIED = 2,     /* :733-751, through the reference keyframe's pose before and after */
+    SIVO_GBA_POINT_REF_OUTSIDE = 3  /* :737, untouched */
+};
+
+typedef struct {
+    int32_t n_kf;
+    int32_t n_origins;
+    int32_t n_points;
+    const int32_t *origin;     /* n_origins: mvpKeyFrameOrigins */
+    const int64_t *child_off;  /* n_kf + 1, CSR over GetChildren() (as in SivoLocalMapTables) */
+    const int32_t *child_kf;
+    const float *tcw;          /* 16 n_kf: GetPose(); GetPoseInverse() is derived from it by KeyFrame::SetPose's rules */
+    float *tcw_gba;            /* in/out, 16 n_kf: mTcwGBA */
+    uint8_t *in_gba;           /* in/out, n_kf: mnBAGlobalForKF == nLoopKF */
+    float *tcw_bef;            /* in/out, 16 n_kf: mTcwBefGBA */
+    const float *pos;          /* 3 n_points: GetWorldPos() */
+    const float *pos_gba;      /* 3 n_points: mPosGBA */
+    const uint8_t *point_in_gba; /* n_points: mnBAGlobalForKF == nLoopKF */
+    const uint8_t *point_bad;  /* n_points: isBad() */
+    const int32_t *ref_kf;     /* n_points: GetReferenceKeyFrame(); -1 only for a bad point or one the BA holds */
+    float *tcw_out;            /* out, 16 n_kf: the pose SetPose receives; written for the reached keyframes only */
+    float *ow_out;             /* out, 3 n_kf: its camera centre; likewise */
+    uint8_t *kf_reached;       /* out, n_kf: the walk from the origins came by */
+    float *pos_out;            /* out, 3 n_points: written for SIVO_GBA_POINT_FROM_BA and SIVO_GBA_POINT_CARRIED only */
+    uint8_t *point_status;     /* out, n_points: SIVO_GBA_POINT_* */
+} SivoGbaPropagate;
+
+/* LoopClosing.cc:695-753 on arrays.  The walk from the origins through the children: a reached keyframe outside the BA
+ * gets tcw_gba = (tcw_child * Twc_parent) * tcw_gba_parent — two float gemms on the parent's pose and inverse from
+ * before its SetPose — and in_gba = 1; every reached keyframe gets tcw_bef = tcw and tcw_out = tcw_gba (an origin
+ * outside the BA with its stale tcw_gba, as the reference); unreached keyframes keep everything.  The points read
+ * in_gba after the walk: Xc = Rcw_bef * P + tcw_bef, pos_out = Rwc * Xc + twc with the reference keyframe's new inverse
+ * pose, each one gemm.  Also refused: a keyframe listed as a child more than once, an origin that is somebody's child
+ * or is listed twice, a cycle among the children (the kernels walk the tree), ref_kf < 0 for a point that would be
+ * carried. */
+int sivo_gba_propagate(const SivoGbaPropagate *problem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,8 @@ SIGNATURES = {
     "sivo_essential_graph_optimize": [_vp, _vp, _i, _vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_essential_graph_analyze": [_vp, _i, _vp, _i, _vp],
     "sivo_sim3_correct_points": [_vp, _vp, _i, _vp, _vp, _i, _vp],
+    "sivo_loop_correct": [_vp],
+    "sivo_gba_propagate": [_vp],
     "sivo_ba_linearize_dev": [_vp, _vp, _vp, _i64, C.POINTER(_d), _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sivo_ba_linearize": [_vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
