@@ -968,6 +968,52 @@ int sivo_search_local_points(sivo_mframe_t F, const SivoFrustum *frustum, int n,
                              int *n_to_match, int *n_matches);
 
 /* ===========================================================================
+ * ORBmatcher::Fuse for a list of map points into EVERY target keyframe in one call:
+ * the loops of LocalMapping::SearchInNeighbors (reference LocalMapping.cc:586-594)
+ * and LoopClosing::SearchAndFuse (LoopClosing.cc:609-635) up to the choice of the
+ * keypoint.  The per-point tests of ORBmatcher.cc:814-852 / :966-1006 (projection,
+ * image, distance, viewing angle, PredictScale) and the window query run on the
+ * device, one wave per (keyframe, point) pair; the Replace / AddObservation surgery
+ * is the caller's (SIVO::FuseIntoKeyFrames / SIVO::SearchAndFuse replay it in the
+ * reference's order).  DESIGN 3.6k.
+ * ======================================================================== */
+typedef struct {
+    float Rcw[9], tcw[3];             /* Tcw form: GetRotation / GetTranslation; Scw form: sRcw / s and t / s, as matcher_detail::Pose(Scw, s) */
+    float Ow[3];                      /* Tcw form: GetCameraCenter() as stored; Scw form: -Rcw' tcw as Pose::centre */
+    float fx, fy, cx, cy, bf;
+    float min_x, max_x, min_y, max_y;
+    float log_scale_factor;           /* > 0 */
+    int32_t nlevels;                  /* 1 .. 16, not above the frame's */
+    int32_t scw_variant;              /* as sivo_fuse's argument */
+} SivoFuseCamera;                     /* 108 bytes */
+
+enum { SIVO_FUSE_MATCHED = 0, SIVO_FUSE_SKIPPED, SIVO_FUSE_BEHIND, SIVO_FUSE_IMAGE, SIVO_FUSE_DISTANCE,
+       SIVO_FUSE_ANGLE, SIVO_FUSE_NO_CANDIDATE, SIVO_FUSE_TOO_FAR };   /* the `continue` the pair took; TOO_FAR: bestDist > TH_LOW */
+
+/* kfs / cams: n_kf frames and their cameras.  pos, normal (3 n_mp each), min_dist,
+ * max_dist = mfMinDistance / mfMaxDistance (the factors 0.8f and 1.2f are applied
+ * inside), mp_desc (32 n_mp).  skip_point[i] != 0: point i takes part in no pair;
+ * skip_pair[k * n_mp + i] != 0: that pair is skipped (both may be NULL).
+ * Outputs are row-major by keyframe: best_idx[k * n_mp + i] = the keypoint of
+ * keyframe k that point i fuses with or -1, for every pair what sivo_fuse on keyframe
+ * k gives for the host projection of that point; best_dist as sivo_fuse (256, resp.
+ * INT_MAX in the Scw form, where no candidate was compared); status = SIVO_FUSE_*.
+ * u, v, ur, level (each may be NULL) are written for the pairs that reach the window
+ * query (status MATCHED, NO_CANDIDATE, TOO_FAR) and left alone otherwise.
+ * Negative counts, a NULL required array with a positive count, a NULL frame, frames
+ * on different devices, nlevels outside [1, 16] or above the frame's, or
+ * log_scale_factor <= 0 -> SIVO_ERR_INVALID_ARGUMENT before any device is touched,
+ * nothing written.  n_kf == 0 or n_mp == 0 succeeds and launches nothing.  Every
+ * frame must be free of other calls for the duration (a frame serves one search at
+ * a time); they are usable by sivo_fuse / sivo_search again when the call returns. */
+int sivo_fuse_batch(const sivo_mframe_t *kfs, const SivoFuseCamera *cams, int n_kf, int n_mp,
+                    const float *pos, const float *normal, const float *min_dist, const float *max_dist,
+                    const uint8_t *mp_desc, const uint8_t *skip_point /* n_mp or NULL */,
+                    const uint8_t *skip_pair /* n_kf * n_mp or NULL */, float th,
+                    int32_t *best_idx, int32_t *best_dist, uint8_t *status,
+                    float *u, float *v, float *ur, int32_t *level /* each n_kf * n_mp, each may be NULL */);
+
+/* ===========================================================================
  * Covisibility bookkeeping: KeyFrame::UpdateConnections (reference
  * src/orbslam/KeyFrame.cc:327-415), the vote of Tracking::UpdateLocalKeyFrames
  * (Tracking.cc:1126-1142), LocalMapping::KeyFrameCulling (LocalMapping.cc:727-792)

@@ -119,6 +119,12 @@ class Frustum(C.Structure):  # == SivoFrustum (96 bytes): the camera of sivo_fru
                 ("log_scale_factor", C.c_float), ("nlevels", C.c_int32), ("cos_limit", C.c_float)]
 
 
+class FuseCamera(C.Structure):  # == SivoFuseCamera (108 bytes): one keyframe's camera of sivo_fuse_batch
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("bf", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("log_scale_factor", C.c_float), ("nlevels", C.c_int32), ("scw_variant", C.c_int32)]
+
+
 class Sim3Edge(C.Structure):   # == SivoSim3Edge (72 bytes): one EdgeSim3 of sivo_essential_graph_optimize
     _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("meas", C.c_double * 8)]
 
@@ -189,6 +195,7 @@ SIGNATURES = {
     "sivo_search_by_projection_reloc": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _pi32],
     "sivo_search_by_projection_kf": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _pi32],
     "sivo_fuse": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _pi32],
+    "sivo_fuse_batch": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sivo_search_by_sim3_dir": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp],
     "sivo_search_by_bow_kf_frame": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _i, _vp, _pi32],
     "sivo_search_by_bow_kf_kf": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _vp, _pi32],

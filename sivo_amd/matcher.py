@@ -177,6 +177,46 @@ def fuse(KF, valid, u, v, ur, pred_level, mp_desc, th, scw_variant):
     return nf.value, bi, bd
 
 
+FUSE_STATUS = ("matched", "skipped", "behind", "image", "distance", "angle", "no_candidate", "too_far")    # SIVO_FUSE_*
+FUSE_CAMERA_DTYPE = np.dtype([("Rcw", np.float32, 9), ("tcw", np.float32, 3), ("Ow", np.float32, 3), ("fx", np.float32), ("fy", np.float32),
+                              ("cx", np.float32), ("cy", np.float32), ("bf", np.float32), ("min_x", np.float32), ("max_x", np.float32),
+                              ("min_y", np.float32), ("max_y", np.float32), ("log_scale_factor", np.float32), ("nlevels", np.int32),
+                              ("scw_variant", np.int32)])          # == SivoFuseCamera / _lib.FuseCamera
+
+
+def fuse_batch(frames, cams, pos, normal, min_dist, max_dist, mp_desc, th, skip_point=None, skip_pair=None, extras=True):
+    """ORBmatcher::Fuse of one list of map points into every keyframe of `frames` (MatchFrame) in one device call (sivo_fuse_batch):
+    the per-point tests of ORBmatcher.cc:814-852 / :966-1006 and the choice of the keypoint, up to the surgery.  cams: one
+    FUSE_CAMERA_DTYPE record (or _lib.FuseCamera) per frame.  Returns a dict of (n_kf, n_mp) arrays: best_idx, best_dist, status
+    (index into FUSE_STATUS) and, with extras, u / v / ur / level (NaN / -1 where the pair did not reach the window query)."""
+    K = len(frames)
+    if isinstance(cams, np.ndarray):
+        cams = _a(cams, FUSE_CAMERA_DTYPE)
+    else:
+        cams = np.frombuffer(b"".join(bytes(c) for c in cams), FUSE_CAMERA_DTYPE) if K else np.zeros(0, FUSE_CAMERA_DTYPE)
+    if len(cams) != K:
+        raise ValueError("fuse_batch: one camera per frame")
+    pos, normal = _a(pos, np.float32).reshape(-1, 3), _a(normal, np.float32).reshape(-1, 3)
+    N = len(pos)
+    min_dist, max_dist, mp_desc = _a(min_dist, np.float32), _a(max_dist, np.float32), _a(mp_desc, np.uint8)
+    if not (len(normal) == N and min_dist.size == N and max_dist.size == N and mp_desc.size == 32 * N):
+        raise ValueError("fuse_batch: the point arrays differ in length")
+    sp = None if skip_point is None else _a(skip_point, np.uint8)
+    sq = None if skip_pair is None else _a(skip_pair, np.uint8)
+    if (sp is not None and sp.size != N) or (sq is not None and sq.size != K * N):
+        raise ValueError("fuse_batch: a skip mask of the wrong size")
+    handles = (C.c_void_p * max(K, 1))(*[f._h for f in frames])
+    out = {"best_idx": np.full((K, N), -1, np.int32), "best_dist": np.zeros((K, N), np.int32), "status": np.zeros((K, N), np.uint8)}
+    if extras:
+        out.update(u=np.full((K, N), np.nan, np.float32), v=np.full((K, N), np.nan, np.float32), ur=np.full((K, N), np.nan, np.float32),
+                   level=np.full((K, N), -1, np.int32))
+    L = frames[0]._L if K else lib()
+    check(L.sivo_fuse_batch(handles, _p(cams), K, N, _p(pos), _p(normal), _p(min_dist), _p(max_dist), _p(mp_desc), _p(sp), _p(sq), float(th),
+                            _p(out["best_idx"]), _p(out["best_dist"]), _p(out["status"]), _p(out.get("u")), _p(out.get("v")),
+                            _p(out.get("ur")), _p(out.get("level"))))
+    return out
+
+
 def search_by_sim3_dir(KF, valid, u, v, pred_level, mp_desc, th):
     """One direction of ORBmatcher::SearchBySim3 (ORBmatcher.cc:1102-1176)."""
     out = np.empty(len(u), np.int32)
