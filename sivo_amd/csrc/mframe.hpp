@@ -1,4 +1,6 @@
-// mframe.hpp — the device side of a frame (sivo_mframe_t): what search.hip builds and owns, and what fuse_batch.hip reads of it.
+// mframe.hpp — the device side of a frame (sivo_mframe_t): what search.hip builds and owns, the view of it that a kernel reads
+// (MframeView: search.hip's rounds, fuse_batch.hip's table of keyframes), and the device helpers every guided matcher shares: the window
+// walk of Frame::GetFeaturesInArea over the frame's grid (scan_window), the (distance, visiting order) key and the Hamming distance.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,9 +9,8 @@
 #include <vector>
 
 #include "../../include/sivo_hip.h"
+#include "grid_math.hpp"
 
-#define SIVO_GRID_COLS 64   // FRAME_GRID_COLS (reference include/orbslam/Frame.h:38-39)
-#define SIVO_GRID_ROWS 48
 #define SIVO_TH_HIGH 100
 #define SIVO_TH_LOW 50
 
@@ -30,6 +31,17 @@ struct MframeSlab {
     }
 };
 
+namespace sivo {
+// What a kernel reads of one frame: pointers into its slab, the grid's bounds, the key count.
+struct MframeView {
+    const float *x, *y, *angle, *ur, *scale, *sigma2, *inv_sigma2;     // ur: null for a frame without mvRight
+    const int32_t *oct, *cell_off, *cell_idx;
+    const uint4 *desc;
+    float min_x, min_y, inv_w, inv_h;
+    int32_t n;
+};
+}  // namespace sivo
+
 struct sivo_mframe {
     int device = 0, n = 0, nlevels = 0;
     float min_x = 0, max_x = 0, min_y = 0, max_y = 0, inv_w = 0, inv_h = 0;
@@ -45,10 +57,36 @@ struct sivo_mframe {
     int32_t *d_oct = nullptr, *d_cell_off = nullptr, *d_cell_idx = nullptr;
     uint4 *d_desc = nullptr;
     hipStream_t stream = nullptr;
+    // The only place that reads the d_* members for a kernel.  A view taken before the engine's scratch() is stale: scratch() can move
+    // the frame to a bigger slab, which rebinds every pointer (and the stream).
+    sivo::MframeView view() const {
+        return sivo::MframeView{d_x, d_y, d_angle, u_right.empty() ? nullptr : d_ur, d_scale, d_sigma2, d_inv_sigma2, d_oct, d_cell_off,
+                                d_cell_idx, d_desc, min_x, min_y, inv_w, inv_h, n};
+    }
     ~sivo_mframe();
 };
 
 namespace sivo {
+// Frame::GetFeaturesInArea's walk, the lane's share: visit(idx, order) for every 64th key of the CSR spans the window covers, column by
+// column; `order` is the key's position in the reference's walk.  The walk yields every key of the covered CELLS: the in_window test
+// (grid_math.hpp) is the visitor's, which may have cheaper rejections to make first.
+template <class Visit>
+__device__ __forceinline__ void scan_window(const MframeView &V, float u, float v, float r, int lane, Visit visit) {
+    int cx0, cx1, cy0, cy1;
+    if (!grid_window(V.min_x, V.min_y, V.inv_w, V.inv_h, u, v, r, cx0, cx1, cy0, cy1)) return;
+    uint32_t base = 0;
+    for (int ix = cx0; ix <= cx1; ++ix) {
+        const int s = V.cell_off[ix * SIVO_GRID_ROWS + cy0], e = V.cell_off[ix * SIVO_GRID_ROWS + cy1 + 1];
+        for (int j = s + lane; j < e; j += 64) visit(V.cell_idx[j], base + (uint32_t)(j - s));
+        base += (uint32_t)(e - s);
+    }
+}
+
+// The key a wave minimises: distance, then visiting order (< 2^22: the callers' limit on keys and list entries) — the reference's
+// first-minimum-wins scan; a caller whose LAST minimum wins passes the order's complement.
+constexpr uint32_t KEY_NONE = 0xffffffffu;
+__device__ __forceinline__ uint32_t match_key(int d, uint32_t order) { return ((uint32_t)d << 22) | order; }
+
 __device__ __forceinline__ int ham256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1) {
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
            __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);

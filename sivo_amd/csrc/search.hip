@@ -7,7 +7,9 @@
 // grid column in a CSR laid out column-major like the reference's mGrid[ix][iy] walk, so a window is <= 2r/16+2 spans
 // that the 64 lanes stride over (coalesced index loads, 2 x 16-byte descriptor loads per candidate, v_bcnt for the
 // distance, wave-butterfly for best / second best on a (distance, visiting order) key, which reproduces the
-// reference's first-minimum-wins scans bit for bit).
+// reference's first-minimum-wins scans bit for bit).  The frame's view, the window walk and the key are mframe.hpp's (MframeView,
+// scan_window, match_key), the grid arithmetic and Fuse's chi-square gate grid_math.hpp's: fuse_batch.hip runs the same ones.  The host
+// side stages through Layout (solver_host.hpp): frame_layout for a frame's arrays at the head of its slab, engine_layout for a call.
 //
 // Sequential semantics.  In the reference, iteration i of a routine skips keypoints matched by iterations < i.  Here all
 // queries run at once against the initial state ("round 0"); accepted picks are registered with atomics, and only if
@@ -23,13 +25,13 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
-#include <type_traits>
 #include <stdexcept>
 #include <vector>
 
 #include "common.hpp"
 #include "frustum_math.hpp"
 #include "mframe.hpp"
+#include "solver_host.hpp"
 
 #define SIVO_HISTO 30       // ORBmatcher::HISTO_LENGTH
 
@@ -37,12 +39,7 @@ namespace sivo {
 namespace {
 
 struct SearchArgs {
-    // train frame
-    int n;
-    const float *x, *y, *angle, *ur, *scale, *sigma2, *inv_sigma2;
-    const int32_t *oct, *cell_off, *cell_idx;
-    const uint4 *desc;
-    float min_x, min_y, inv_w, inv_h;
+    MframeView V;                // train frame
     // queries
     int nq;
     const SivoSearchQuery *q;
@@ -57,9 +54,8 @@ struct SearchArgs {
     int32_t *flags;              // [0] collision (two accepted picks of one keypoint), [1] a pick changed
 };
 
-// top-2 of a (key, index) multiset; key = dist << 22 | visiting order (or its complement when the last candidate wins)
+// top-2 of a (key, index) multiset; key = match_key of the distance and the visiting order (or its complement when the last candidate wins)
 struct Top2 { uint32_t k1, k2; int i1, i2; };
-constexpr uint32_t KEY_NONE = 0xffffffffu;
 __device__ __forceinline__ void top2_push(Top2 &t, uint32_t k, int i) {
     if (k < t.k1) { t.k2 = t.k1; t.i2 = t.i1; t.k1 = k; t.i1 = i; }
     else if (k < t.k2) { t.k2 = k; t.i2 = i; }
@@ -74,44 +70,32 @@ __global__ __launch_bounds__(256) void search_round_kernel(SearchArgs a) {
     if (Q.flags & SIVO_Q_VALID) {
         const uint4 q0 = a.qdesc[(int64_t)qi * 2], q1 = a.qdesc[(int64_t)qi * 2 + 1];
         const int gate = a.rule.gate_mode;
+        const MframeView &V = a.V;
         // one candidate (lane-local): static gates, dynamic exclusion, distance
         auto visit = [&](int idx, uint32_t ord) {
             if (a.blocked && a.blocked[idx]) return;
             if (a.owner_prev && a.owner_prev[idx] < qi) return;
-            const int lvl = a.oct[idx];
+            const int lvl = V.oct[idx];
             if (lvl < Q.lvl_lo || lvl > Q.lvl_hi) return;
-            const float kx = a.x[idx], ky = a.y[idx];
-            if (!a.cidx) {
-                // GetFeaturesInArea (Frame.cc:379-384)
-                const float distx = kx - Q.u, disty = ky - Q.v;
-                if (!(fabsf(distx) < Q.radius && fabsf(disty) < Q.radius)) return;
-            }
-            const float kur = a.ur ? a.ur[idx] : -1.0f;
+            const float kx = V.x[idx], ky = V.y[idx];
+            if (!a.cidx && !in_window(kx, ky, Q.u, Q.v, Q.radius)) return;
+            const float kur = V.ur ? V.ur[idx] : -1.0f;
             if (gate == 1) {
                 if (kur > 0) {
                     const float er = fabsf(Q.ur - kur);
                     if (er > Q.gate) return;
                 }
             } else if (gate == 2) {
-                // Fuse (ORBmatcher.cc:880-902)
-                const float ex = Q.u - kx, ey = Q.v - ky;
-                if (kur >= 0) {
-                    const float er = Q.ur - kur;
-                    const float e2 = ex * ex + ey * ey + er * er;
-                    if ((double)(e2 * a.inv_sigma2[lvl]) > 7.8) return;
-                } else {
-                    const float e2 = ex * ex + ey * ey;
-                    if ((double)(e2 * a.inv_sigma2[lvl]) > 5.99) return;
-                }
+                if (!fuse_chi2_gate(Q.u - kx, Q.v - ky, kur >= 0, Q.ur - kur, V.inv_sigma2[lvl])) return;      // Fuse
             }
-            const int d = ham256(q0, q1, a.desc[(int64_t)idx * 2], a.desc[(int64_t)idx * 2 + 1]);
+            const int d = ham256(q0, q1, V.desc[(int64_t)idx * 2], V.desc[(int64_t)idx * 2 + 1]);
             if (gate == 3) {
                 // SearchForTriangulation (ORBmatcher.cc:703-719)
                 if (d > a.rule.th_dist) return;
                 const bool st1 = (Q.flags & SIVO_Q_STEREO) != 0, st2 = kur >= 0;
                 if (!st1 && !st2) {
                     const float distex = a.rule.ex - kx, distey = a.rule.ey - ky;
-                    if (distex * distex + distey * distey < 100 * a.scale[lvl]) return;
+                    if (distex * distex + distey * distey < 100 * V.scale[lvl]) return;
                 }
                 const float *F = a.rule.F12;
                 const float ea = Q.u * F[0] + Q.v * F[3] + F[6];
@@ -121,29 +105,17 @@ __global__ __launch_bounds__(256) void search_round_kernel(SearchArgs a) {
                 const float den = ea * ea + eb * eb;
                 if (den == 0) return;
                 const float dsqr = num * num / den;
-                if (!((double)dsqr < 3.84 * (double)a.sigma2[lvl])) return;
+                if (!((double)dsqr < 3.84 * (double)V.sigma2[lvl])) return;
             }
             if (d >= 256) return;                        // bestDist starts at 256 and the test is `dist < bestDist`
             const uint32_t o = a.rule.tie_last ? (0x3fffffu - ord) : ord;
-            top2_push(t, ((uint32_t)d << 22) | o, idx);
+            top2_push(t, match_key(d, o), idx);
         };
         if (a.cidx) {
             const int s = a.cbeg[qi], e = a.cend[qi];
             for (int j = s + lane; j < e; j += 64) visit(a.cidx[j], (uint32_t)(j - s));
         } else {
-            // window -> cell ranges, exactly as Frame::GetFeaturesInArea (Frame.cc:334-357)
-            int cx0 = max(0, (int)floorf((Q.u - a.min_x - Q.radius) * a.inv_w));
-            int cx1 = min(SIVO_GRID_COLS - 1, (int)ceilf((Q.u - a.min_x + Q.radius) * a.inv_w));
-            int cy0 = max(0, (int)floorf((Q.v - a.min_y - Q.radius) * a.inv_h));
-            int cy1 = min(SIVO_GRID_ROWS - 1, (int)ceilf((Q.v - a.min_y + Q.radius) * a.inv_h));
-            if (cx0 < SIVO_GRID_COLS && cx1 >= 0 && cy0 < SIVO_GRID_ROWS && cy1 >= 0) {
-                uint32_t base = 0;
-                for (int ix = cx0; ix <= cx1; ++ix) {
-                    const int s = a.cell_off[ix * SIVO_GRID_ROWS + cy0], e = a.cell_off[ix * SIVO_GRID_ROWS + cy1 + 1];
-                    for (int j = s + lane; j < e; j += 64) visit(a.cell_idx[j], base + (uint32_t)(j - s));
-                    base += (uint32_t)(e - s);
-                }
-            }
+            scan_window(V, Q.u, Q.v, Q.radius, lane, visit);
         }
     }
     // butterfly: merge the lanes' top-2 sets
@@ -158,7 +130,7 @@ __global__ __launch_bounds__(256) void search_round_kernel(SearchArgs a) {
     const int best = t.i1 >= 0 ? (int)(t.k1 >> 22) : 256, second = t.i2 >= 0 ? (int)(t.k2 >> 22) : 256;
     bool accept = t.i1 >= 0 && (a.rule.accept_lt ? best < a.rule.th_dist : best <= a.rule.th_dist);
     if (accept && a.rule.ratio_mode == 1) {
-        const int bestLevel = a.oct[t.i1], bestLevel2 = t.i2 >= 0 ? a.oct[t.i2] : -1;
+        const int bestLevel = a.V.oct[t.i1], bestLevel2 = t.i2 >= 0 ? a.V.oct[t.i2] : -1;
         if (bestLevel == bestLevel2 && (float)best > a.rule.nn_ratio * (float)second) accept = false;
     } else if (accept && a.rule.ratio_mode == 2) {
         if (!((float)best < a.rule.nn_ratio * (float)second)) accept = false;
@@ -249,13 +221,6 @@ __global__ __launch_bounds__(1024) void search_finalize_kernel(FinalArgs a) {
     if (culled) atomicAdd(&a.counters[1], culled);
 }
 
-template <class T>
-T *carve(char *&p, size_t count) {
-    T *r = reinterpret_cast<T *>(p);
-    p += (count * sizeof(T) + 255) / 256 * 256;
-    return r;
-}
-
 // ---- slab pool ------------------------------------------------------------------------------------------------------
 struct SlabPool {
     std::mutex mu;
@@ -293,16 +258,16 @@ SlabPool &slab_pool() {
     return *p;
 }
 
-// Lays the frame's arrays out in the slab (device pointers into F, the same offsets in the pinned mirror); returns the bytes used.
-size_t bind_frame(sivo_mframe &F, char *base) {
-    char *p = base;
-    const size_t n = (size_t)F.n;
-    F.d_x = carve<float>(p, n); F.d_y = carve<float>(p, n); F.d_angle = carve<float>(p, n); F.d_oct = carve<int32_t>(p, n);
-    F.d_ur = carve<float>(p, F.u_right.size());
-    F.d_desc = carve<uint4>(p, n * 2);
-    F.d_cell_off = carve<int32_t>(p, F.cell_off.size()); F.d_cell_idx = carve<int32_t>(p, F.cell_idx.size());
-    F.d_scale = carve<float>(p, (size_t)F.nlevels); F.d_sigma2 = carve<float>(p, (size_t)F.nlevels); F.d_inv_sigma2 = carve<float>(p, (size_t)F.nlevels);
-    return (size_t)(p - base);
+// The frame's arrays at the head of a slab: place() on (slab->d, slab->h) binds F's device pointers, bytes() is F.frame_bytes.
+Layout frame_layout(sivo_mframe &F) {
+    Layout L;
+    const size_t n = (size_t)F.n, lv = 4 * (size_t)F.nlevels;
+    L.copy(F.d_x, nullptr, 4 * n); L.copy(F.d_y, nullptr, 4 * n); L.copy(F.d_angle, nullptr, 4 * n); L.copy(F.d_oct, nullptr, 4 * n);
+    L.copy(F.d_ur, nullptr, 4 * F.u_right.size());
+    L.copy(F.d_desc, nullptr, 32 * n);
+    L.copy(F.d_cell_off, nullptr, 4 * F.cell_off.size()); L.copy(F.d_cell_idx, nullptr, 4 * F.cell_idx.size());
+    L.copy(F.d_scale, nullptr, lv); L.copy(F.d_sigma2, nullptr, lv); L.copy(F.d_inv_sigma2, nullptr, lv);
+    return L;
 }
 
 // The engine's scratch behind the frame's arrays; a call that needs more than the slab holds moves the frame to a bigger slab
@@ -316,25 +281,58 @@ char *scratch(sivo_mframe &F, size_t bytes) {
         slab_pool().give(std::move(F.slab));
         F.slab = std::move(big);
         F.stream = F.slab->stream;
-        bind_frame(F, F.slab->d);
+        frame_layout(F).place(F.slab->d, F.slab->h);
     }
     return F.slab->d + F.frame_bytes;
 }
 
-// Queries made on the device (sivo_search_local_points): the engine carves `up_bytes` more into its upload block and `down_bytes` more
-// into its download block, the producer stages its inputs into the mirror of the former, enqueues its kernel behind the upload — it
-// writes all nq query records — and reads its own results from the mirror of the latter once the engine has synchronised.
-// Contract: with nq > 0 the engine calls stage, launch and collect, once each and in that order; with nq <= 0 it returns before it
+// Queries made on the device (sivo_search_local_points): the producer adds its inputs (copy regions) and its results (take regions) to
+// the engine's layout, enqueues its kernel behind the upload — it writes all nq query records — and reads its own results from the
+// mirror once the engine has synchronised.
+// Contract: with nq > 0 the engine calls regions, launch and collect, once each and in that order; with nq <= 0 it returns before it
 // takes any scratch and calls none of them (there is nothing to stage or collect).  scratch() may move the frame to a bigger slab, so
-// every device pointer of the frame (d_scale, ...) and its stream are valid only from launch on: launch takes them from the frame it
-// is handed, never from a copy made before run_search.
+// the frame's view and its stream are valid only from launch on: launch takes them from the frame it is handed, never from a copy made
+// before run_search.
 struct DeviceQueries {
-    size_t up_bytes = 0, down_bytes = 0;
-    virtual void stage(char *h_up) = 0;
-    virtual void launch(const sivo_mframe &F, SivoSearchQuery *d_q, char *d_up, char *d_down) = 0;
-    virtual void collect(const char *h_down) = 0;
+    virtual void regions(Layout &L) = 0;
+    virtual void launch(const sivo_mframe &F, SivoSearchQuery *d_q) = 0;
+    virtual void collect(const Layout &L) = 0;
     virtual ~DeviceQueries() {}
 };
+
+struct EngineIn {                // the host arrays of a call (all null where only the size of the layout is asked for)
+    const SivoSearchQuery *q;
+    const uint8_t *qdesc;
+    const int32_t *cbeg, *cend, *cidx;
+    const uint8_t *blocked;
+};
+struct EngineBufs {              // what the layout hands out beside the pointers that live in SearchArgs
+    SivoSearchQuery *q;
+    int32_t *owner[2];           // [1]: device only
+    int32_t *counters, *match_query, *match_train;
+    size_t down;                 // the results to copy back, from `counters` on
+};
+
+// The engine's regions of one call, the only statement of its scratch: [ upload | results | device-only ].  The upload holds the
+// queries, their descriptors, the candidate lists (`lists`), the blocked flags and the regions that START with a value the caller
+// writes through L.host() — pick, flags and, for a dynamic rule, owner[0] and npick; the results hold the producer's as well.
+void engine_layout(Layout &L, SearchArgs &a, EngineBufs &b, int n, int nq, int n_cand, bool dynamic, bool lists, DeviceQueries *dq,
+                   const EngineIn &in = EngineIn{}) {
+    const size_t N = (size_t)n, Q = (size_t)nq;
+    L.copy(b.q, in.q, Q * sizeof(SivoSearchQuery));                 // (with dq: written by its kernel)
+    L.copy(a.qdesc, in.qdesc, 32 * Q);
+    L.copy(a.cbeg, in.cbeg, 4 * Q); L.copy(a.cend, in.cend, 4 * Q);     // (read with lists only; their room is part of a call's size)
+    if (lists) L.copy(a.cidx, in.cidx, 4 * (size_t)n_cand);
+    L.copy(a.blocked, in.blocked, N);
+    L.copy(a.pick, nullptr, 4 * Q);                                 // -1
+    if (dynamic) { L.copy(b.owner[0], nullptr, 4 * N); L.copy(a.npick, nullptr, 4 * N); }      // 0x7f7f7f7f > any query index; 0
+    L.copy(a.flags, nullptr, 16);                                   // collision, changed: 0
+    L.take(b.counters, 16);                                         // accepted, culled
+    L.take(b.match_query, 4 * Q); L.take(b.match_train, 4 * N); L.take(a.bdist, 4 * Q); L.take(a.sdist, 4 * Q);
+    if (dq) dq->regions(L);
+    b.down = L.results();
+    if (dynamic) L.take(b.owner[1], 4 * N);                         // scratch behind the results: not copied back
+}
 
 // The engine on host arrays: upload queries, rounds, finalize, download.  With `dq` the queries come from the device and `queries` is
 // not read; without it nothing of the layout or the launches changes.
@@ -354,74 +352,41 @@ void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *q
             if ((uint32_t)cand_idx[j] >= (uint32_t)F.n) throw std::invalid_argument("sivo_search: candidate index outside the frame's keypoints");
     DeviceGuard dg(F.device);
     const int n = F.n;
-    const size_t need = 256 * 20 + (size_t)nq * (sizeof(SivoSearchQuery) + 32 + 8 + 4 * 4) + (size_t)(cand_idx ? n_cand : 0) * 4 +
-                        (size_t)(n + 64) * (1 + 4 * 4) + 1024 + (dq ? dq->up_bytes + dq->down_bytes + 512 : 0);
-    // Scratch = [ upload block | device-only | download block ], the pinned mirror has the same layout: ONE copy up (queries,
-    // their descriptors, candidate lists, blocked flags and the initial values of pick / owner / npick / flags), one copy down.
-    char *const d0 = scratch(F, need);
-    char *const h0 = F.slab->h + (d0 - F.slab->d);
-    char *p = d0;
-    SivoSearchQuery *d_q = carve<SivoSearchQuery>(p, nq);
-    uint4 *d_qdesc = carve<uint4>(p, (size_t)nq * 2);
-    int32_t *d_cbeg = carve<int32_t>(p, nq), *d_cend = carve<int32_t>(p, nq);
-    int32_t *d_cidx = carve<int32_t>(p, cand_idx ? n_cand : 0);
-    uint8_t *d_blocked = carve<uint8_t>(p, n);
-    int32_t *d_pick = carve<int32_t>(p, nq);
-    int32_t *d_owner0 = carve<int32_t>(p, rule.dynamic ? n : 0), *d_npick = carve<int32_t>(p, rule.dynamic ? n : 0);
-    int32_t *d_flags = carve<int32_t>(p, 4);     // collision, changed, accepted, culled
-    char *d_dq_up = carve<char>(p, dq ? dq->up_bytes : 0);
-    const size_t up_bytes = (size_t)(p - d0);
-    int32_t *d_owner1 = carve<int32_t>(p, rule.dynamic ? n : 0);
-    if (!rule.dynamic) d_npick = carve<int32_t>(p, n);
-    char *const down0 = p;
-    int32_t *d_counters = carve<int32_t>(p, 4);
-    int32_t *d_mq = carve<int32_t>(p, nq), *d_mtrain = carve<int32_t>(p, n), *d_bd = carve<int32_t>(p, nq), *d_sd = carve<int32_t>(p, nq);
-    char *d_dq_down = carve<char>(p, dq ? dq->down_bytes : 0);
-    const size_t down_bytes = (size_t)(p - down0);
-    int32_t *d_owner[2] = {d_owner0, d_owner1};
-    auto host = [&](auto *dev) { return reinterpret_cast<std::remove_reference_t<decltype(*dev)> *>(h0 + ((char *)dev - d0)); };
+    // ONE copy up (the layout's copy regions, the initial values among them), one copy down (its take regions but the last)
+    SearchArgs a{};
+    EngineBufs b{};
+    Layout L;
+    engine_layout(L, a, b, n, nq, n_cand, rule.dynamic != 0, cand_idx != nullptr, dq,
+                  EngineIn{queries, query_desc, cand_begin, cand_end, cand_idx, blocked});
+    char *const d0 = scratch(F, L.bytes());
     hipStream_t st = F.stream;
     SIVO_HIP(hipStreamSynchronize(st));          // (the mirror may still feed the frame's own upload)
-    if (dq) dq->stage(host(d_dq_up));
-    else std::memcpy(host(d_q), queries, (size_t)nq * sizeof(SivoSearchQuery));
-    std::memcpy(host(d_qdesc), query_desc, (size_t)nq * 32);
-    if (cand_idx) {
-        std::memcpy(host(d_cbeg), cand_begin, (size_t)nq * 4);
-        std::memcpy(host(d_cend), cand_end, (size_t)nq * 4);
-        if (n_cand) std::memcpy(host(d_cidx), cand_idx, (size_t)n_cand * 4);
+    L.place(d0, F.slab->h + F.frame_bytes);
+    std::memset(L.host(a.pick), 0xff, (size_t)nq * 4);
+    if (rule.dynamic) {
+        std::memset(L.host(b.owner[0]), 0x7f, (size_t)n * 4);
+        std::memset(L.host(a.npick), 0, (size_t)n * 4);
     }
-    if (blocked && n) std::memcpy(host(d_blocked), blocked, (size_t)n);
-    std::memset(host(d_pick), 0xff, (size_t)nq * 4);        // -1
-    if (rule.dynamic && n) {
-        std::memset(host(d_owner0), 0x7f, (size_t)n * 4);    // 0x7f7f7f7f > any query index
-        std::memset(host(d_npick), 0, (size_t)n * 4);
-    }
-    std::memset(host(d_flags), 0, 16);
-    SIVO_HIP(hipMemcpyAsync(d0, h0, up_bytes, hipMemcpyHostToDevice, st));
-    if (dq) dq->launch(F, d_q, d_dq_up, d_dq_down);
+    std::memset(L.host(a.flags), 0, 16);
+    L.send(st);
+    if (dq) dq->launch(F, b.q);
 
-    SearchArgs a{};
-    a.n = n; a.x = F.d_x; a.y = F.d_y; a.angle = F.d_angle; a.ur = F.u_right.empty() ? nullptr : F.d_ur;
-    a.scale = F.d_scale; a.sigma2 = F.d_sigma2; a.inv_sigma2 = F.d_inv_sigma2;
-    a.oct = F.d_oct; a.cell_off = F.d_cell_off; a.cell_idx = F.d_cell_idx; a.desc = F.d_desc;
-    a.min_x = F.min_x; a.min_y = F.min_y; a.inv_w = F.inv_w; a.inv_h = F.inv_h;
-    a.nq = nq; a.q = d_q; a.qdesc = d_qdesc;
-    a.cbeg = d_cbeg; a.cend = d_cend; a.cidx = cand_idx ? d_cidx : nullptr;
-    a.rule = rule; a.blocked = blocked ? d_blocked : nullptr;
-    a.npick = d_npick; a.pick = d_pick; a.bdist = d_bd; a.sdist = d_sd; a.flags = d_flags;
+    a.V = F.view();
+    a.nq = nq; a.q = b.q; a.rule = rule;
+    if (!blocked) a.blocked = nullptr;
     int rounds = 0;
     for (;; ++rounds) {
-        a.owner_prev = rounds == 0 ? nullptr : d_owner[(rounds + 1) & 1];
-        a.owner_next = d_owner[rounds & 1];
+        a.owner_prev = rounds == 0 ? nullptr : b.owner[(rounds + 1) & 1];
+        a.owner_next = b.owner[rounds & 1];
         if (rounds && rule.dynamic && n) {                                         // (round 0's values came with the upload)
             SIVO_HIP(hipMemsetAsync(a.owner_next, 0x7f, (size_t)n * 4, st));
-            SIVO_HIP(hipMemsetAsync(d_npick, 0, (size_t)n * 4, st));
+            SIVO_HIP(hipMemsetAsync(a.npick, 0, (size_t)n * 4, st));
         }
-        if (rounds) SIVO_HIP(hipMemsetAsync(d_flags, 0, 8, st));
+        if (rounds) SIVO_HIP(hipMemsetAsync(a.flags, 0, 8, st));
         hipLaunchKernelGGL(search_round_kernel, dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, st, a);
         if (!rule.dynamic) { ++rounds; break; }
-        int32_t *fl = host(d_flags);
-        SIVO_HIP(hipMemcpyAsync(fl, d_flags, 8, hipMemcpyDeviceToHost, st));
+        int32_t *fl = L.host(a.flags);
+        SIVO_HIP(hipMemcpyAsync(fl, a.flags, 8, hipMemcpyDeviceToHost, st));
         SIVO_HIP(hipStreamSynchronize(st));
         // round 0 is final when no keypoint was picked twice — unless a ratio test is on: a keypoint an earlier query took
         // may have been this query's SECOND best, so a confirming round always runs then
@@ -429,33 +394,27 @@ void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *q
         if (rounds > nq + 1) throw std::runtime_error("sivo_search: the repair rounds did not converge");
     }
     FinalArgs f{};
-    f.n = n; f.nq = nq; f.q = d_q; f.angle = F.d_angle; f.pick = d_pick; f.check_orientation = rule.check_orientation;
-    f.match_query = d_mq; f.match_train = d_mtrain; f.counters = d_counters;
+    f.n = n; f.nq = nq; f.q = b.q; f.angle = a.V.angle; f.pick = a.pick; f.check_orientation = rule.check_orientation;
+    f.match_query = b.match_query; f.match_train = b.match_train; f.counters = b.counters;
     hipLaunchKernelGGL(search_finalize_kernel, dim3(1), dim3(1024), 0, st, f);
-    SIVO_HIP(hipMemcpyAsync(h0 + (down0 - d0), down0, down_bytes, hipMemcpyDeviceToHost, st));
+    SIVO_HIP(hipMemcpyAsync(L.host(b.counters), b.counters, b.down, hipMemcpyDeviceToHost, st));
     SIVO_HIP(hipStreamSynchronize(st));
     SIVO_HIP(hipGetLastError());
-    const int32_t *cnt = host(d_counters);
-    if (match_query) std::memcpy(match_query, host(d_mq), (size_t)nq * 4);
-    if (match_train && n) std::memcpy(match_train, host(d_mtrain), (size_t)n * 4);
-    if (best_dist) std::memcpy(best_dist, host(d_bd), (size_t)nq * 4);
-    if (second_dist) std::memcpy(second_dist, host(d_sd), (size_t)nq * 4);
+    const int32_t *cnt = L.host(b.counters);
+    if (match_query) std::memcpy(match_query, L.host(b.match_query), (size_t)nq * 4);
+    if (match_train && n) std::memcpy(match_train, L.host(b.match_train), (size_t)n * 4);
+    if (best_dist) std::memcpy(best_dist, L.host(a.bdist), (size_t)nq * 4);
+    if (second_dist) std::memcpy(second_dist, L.host(a.sdist), (size_t)nq * 4);
     if (n_matches) *n_matches = cnt[0] - cnt[1];
     if (rounds_out) *rounds_out = rounds;
-    if (dq) dq->collect(host(d_dq_down));
+    if (dq) dq->collect(L);
 }
 
 // Frame::GetFeaturesInArea (Frame.cc:326-390) on the host copy of the grid.
 void features_in_area(const sivo_mframe &F, float x, float y, float r, int minLevel, int maxLevel, std::vector<int32_t> &out) {
     out.clear();
-    const int nMinCellX = std::max(0, (int)std::floor((x - F.min_x - r) * F.inv_w));
-    if (nMinCellX >= SIVO_GRID_COLS) return;
-    const int nMaxCellX = std::min(SIVO_GRID_COLS - 1, (int)std::ceil((x - F.min_x + r) * F.inv_w));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = std::max(0, (int)std::floor((y - F.min_y - r) * F.inv_h));
-    if (nMinCellY >= SIVO_GRID_ROWS) return;
-    const int nMaxCellY = std::min(SIVO_GRID_ROWS - 1, (int)std::ceil((y - F.min_y + r) * F.inv_h));
-    if (nMaxCellY < 0) return;
+    int nMinCellX, nMaxCellX, nMinCellY, nMaxCellY;
+    if (!grid_window(F.min_x, F.min_y, F.inv_w, F.inv_h, x, y, r, nMinCellX, nMaxCellX, nMinCellY, nMaxCellY)) return;
     const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
     for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
         for (int iy = nMinCellY; iy <= nMaxCellY; iy++)
@@ -465,7 +424,7 @@ void features_in_area(const sivo_mframe &F, float x, float y, float r, int minLe
                     if (kp.octave < minLevel) continue;
                     if (maxLevel >= 0 && kp.octave > maxLevel) continue;
                 }
-                if (std::fabs(kp.x - x) < r && std::fabs(kp.y - y) < r) out.push_back(F.cell_idx[j]);
+                if (in_window(kp.x, kp.y, x, y, r)) out.push_back(F.cell_idx[j]);
             }
 }
 
@@ -537,44 +496,24 @@ struct LocalPointQueries : DeviceQueries {
     float *px, *py, *pxr, *vc;                             // each may be null
     int32_t *level;
     int n_to_match = 0;
-    static size_t al(size_t bytes) { return (bytes + 255) / 256 * 256; }
-    explicit LocalPointQueries(size_t n) : N(n) {
-        up_bytes = 2 * al(12 * N) + 3 * al(4 * N) + al(N);
-        down_bytes = al(N) + 5 * al(4 * N);
+    explicit LocalPointQueries(size_t n) : N(n) {}
+    void regions(Layout &L) override {
+        L.copy(a.pos, pos, 12 * N); L.copy(a.normal, normal, 12 * N); L.copy(a.min_dist, min_dist, 4 * N); L.copy(a.max_dist, max_dist, 4 * N);
+        L.copy(a.obs, obs, 4 * N);
+        a.skip = nullptr;
+        if (skip) L.copy(a.skip, skip, N);
+        L.take(a.status, N); L.take(a.px, 4 * N); L.take(a.py, 4 * N); L.take(a.pxr, 4 * N); L.take(a.vc, 4 * N); L.take(a.level, 4 * N);
     }
-    void stage(char *h) override {
-        std::memcpy(h, pos, 12 * N); h += al(12 * N);
-        std::memcpy(h, normal, 12 * N); h += al(12 * N);
-        std::memcpy(h, min_dist, 4 * N); h += al(4 * N);
-        std::memcpy(h, max_dist, 4 * N); h += al(4 * N);
-        std::memcpy(h, obs, 4 * N); h += al(4 * N);
-        if (skip) std::memcpy(h, skip, N);
-    }
-    void launch(const sivo_mframe &F, SivoSearchQuery *d_q, char *u, char *d) override {
-        a.scale = F.d_scale;                                       // (after scratch(): the frame may have moved to a bigger slab)
-        a.pos = (const float *)u; u += al(12 * N);
-        a.normal = (const float *)u; u += al(12 * N);
-        a.min_dist = (const float *)u; u += al(4 * N);
-        a.max_dist = (const float *)u; u += al(4 * N);
-        a.obs = (const int32_t *)u; u += al(4 * N);
-        a.skip = skip ? (const uint8_t *)u : nullptr;
+    void launch(const sivo_mframe &F, SivoSearchQuery *d_q) override {
+        a.scale = F.view().scale;                                  // (after scratch(): the frame may have moved to a bigger slab)
         a.q = d_q;
-        a.status = (uint8_t *)d; d += al(N);
-        a.px = (float *)d; d += al(4 * N);
-        a.py = (float *)d; d += al(4 * N);
-        a.pxr = (float *)d; d += al(4 * N);
-        a.vc = (float *)d; d += al(4 * N);
-        a.level = (int32_t *)d;
         hipLaunchKernelGGL(fr_queries_kernel, dim3((unsigned)cdiv((int)N, 256)), dim3(256), 0, F.stream, a);
         SIVO_HIP(hipGetLastError());
     }
-    void collect(const char *h) override {
-        const uint8_t *hs = (const uint8_t *)h; h += al(N);
-        const float *hx = (const float *)h; h += al(4 * N);
-        const float *hy = (const float *)h; h += al(4 * N);
-        const float *hr = (const float *)h; h += al(4 * N);
-        const float *hc = (const float *)h; h += al(4 * N);
-        const int32_t *hl = (const int32_t *)h;
+    void collect(const Layout &L) override {
+        const uint8_t *hs = L.host(a.status);
+        const float *hx = L.host(a.px), *hy = L.host(a.py), *hr = L.host(a.pxr), *hc = L.host(a.vc);
+        const int32_t *hl = L.host(a.level);
         for (size_t i = 0; i < N; ++i) {
             status[i] = hs[i];
             if (hs[i] != SIVO_FRUSTUM_IN_VIEW) continue;               // nothing else of the point is written
@@ -620,45 +559,32 @@ extern "C" int sivo_mframe_create(const SivoKeyPoint *keys, int n, const float *
         F->scale.assign(scale_factors, scale_factors + nlevels);
         F->sigma2.assign(level_sigma2, level_sigma2 + nlevels);
         F->inv_sigma2.assign(inv_level_sigma2, inv_level_sigma2 + nlevels);
-        // AssignFeaturesToGrid (Frame.cc:205-221) + PosInGrid (:392-404) -> CSR in mGrid[ix][iy] order
-        const int cells = SIVO_GRID_COLS * SIVO_GRID_ROWS;
-        std::vector<int32_t> cell_of((size_t)n, -1);
-        F->cell_off.assign((size_t)cells + 1, 0);
-        for (int i = 0; i < n; ++i) {
-            require(keys[i].octave >= 0 && keys[i].octave < nlevels, "keypoint octave outside the scale tables");
-            const int px = (int)std::round((keys[i].x - min_x) * F->inv_w), py = (int)std::round((keys[i].y - min_y) * F->inv_h);
-            if (px < 0 || px >= SIVO_GRID_COLS || py < 0 || py >= SIVO_GRID_ROWS) continue;
-            cell_of[i] = px * SIVO_GRID_ROWS + py;
-            ++F->cell_off[cell_of[i] + 1];
-        }
-        for (int c = 0; c < cells; ++c) F->cell_off[c + 1] += F->cell_off[c];
-        F->cell_idx.assign((size_t)F->cell_off[cells], 0);
-        std::vector<int32_t> fill(F->cell_off.begin(), F->cell_off.end() - 1);
-        for (int i = 0; i < n; ++i)
-            if (cell_of[i] >= 0) F->cell_idx[fill[cell_of[i]]++] = i;
+        for (int i = 0; i < n; ++i) require(keys[i].octave >= 0 && keys[i].octave < nlevels, "keypoint octave outside the scale tables");
+        grid_build(keys, n, min_x, min_y, F->inv_w, F->inv_h, F->cell_off, F->cell_idx);
 
         DeviceGuard dg(device);
-        // one slab: the frame's arrays + scratch for a call with as many queries as the frame has keys (a bigger call grows it)
-        const size_t frame_bytes = bind_frame(*F, reinterpret_cast<char *>((uintptr_t)4096));
-        const size_t scratch_guess = 256 * 20 + (size_t)(n + 64) * (sizeof(SivoSearchQuery) + 32 + 8 + 16 + 17) + 1024;
-        F->slab = slab_pool().take(device, frame_bytes + scratch_guess);
+        // one slab: the frame's arrays + the engine's scratch for a dynamic call with candidate lists and as many queries as the
+        // frame has keys (a bigger call grows it)
+        Layout L = frame_layout(*F), guess;
+        SearchArgs ga{};
+        EngineBufs gb{};
+        engine_layout(guess, ga, gb, n, n, 0, true, true, nullptr);
+        F->frame_bytes = L.bytes();
+        F->slab = slab_pool().take(device, F->frame_bytes + guess.bytes());
         F->stream = F->slab->stream;
-        F->frame_bytes = frame_bytes;
-        bind_frame(*F, F->slab->d);
-        char *const h = F->slab->h, *const d = F->slab->d;
-        auto host = [&](auto *dev) { return reinterpret_cast<std::remove_reference_t<decltype(*dev)> *>(h + ((char *)dev - d)); };
-        float *hx = host(F->d_x), *hy = host(F->d_y), *ha = host(F->d_angle);
-        int32_t *ho = host(F->d_oct);
+        L.place(F->slab->d, F->slab->h);
+        float *hx = L.host(F->d_x), *hy = L.host(F->d_y), *ha = L.host(F->d_angle);
+        int32_t *ho = L.host(F->d_oct);
         for (int i = 0; i < n; ++i) { hx[i] = keys[i].x; hy[i] = keys[i].y; ha[i] = keys[i].angle; ho[i] = keys[i].octave; }
-        if (!F->u_right.empty()) std::memcpy(host(F->d_ur), F->u_right.data(), F->u_right.size() * 4);
-        if (n) std::memcpy(host(F->d_desc), descriptors, (size_t)n * 32);
-        std::memcpy(host(F->d_cell_off), F->cell_off.data(), F->cell_off.size() * 4);
-        if (!F->cell_idx.empty()) std::memcpy(host(F->d_cell_idx), F->cell_idx.data(), F->cell_idx.size() * 4);
-        std::memcpy(host(F->d_scale), F->scale.data(), (size_t)nlevels * 4);
-        std::memcpy(host(F->d_sigma2), F->sigma2.data(), (size_t)nlevels * 4);
-        std::memcpy(host(F->d_inv_sigma2), F->inv_sigma2.data(), (size_t)nlevels * 4);
+        if (!F->u_right.empty()) std::memcpy(L.host(F->d_ur), F->u_right.data(), F->u_right.size() * 4);
+        if (n) std::memcpy(L.host(F->d_desc), descriptors, (size_t)n * 32);
+        std::memcpy(L.host(F->d_cell_off), F->cell_off.data(), F->cell_off.size() * 4);
+        if (!F->cell_idx.empty()) std::memcpy(L.host(F->d_cell_idx), F->cell_idx.data(), F->cell_idx.size() * 4);
+        std::memcpy(L.host(F->d_scale), F->scale.data(), (size_t)nlevels * 4);
+        std::memcpy(L.host(F->d_sigma2), F->sigma2.data(), (size_t)nlevels * 4);
+        std::memcpy(L.host(F->d_inv_sigma2), F->inv_sigma2.data(), (size_t)nlevels * 4);
         // (asynchronous: every search of this frame runs on the same stream, behind the upload)
-        SIVO_HIP(hipMemcpyAsync(d, h, frame_bytes, hipMemcpyHostToDevice, F->stream));
+        L.send(F->stream);
         *out = F.release();
         return SIVO_OK;
     });

@@ -2,7 +2,8 @@
 // (sivo_amd/csrc/fuse_math.hpp), with the argument rules of the library (fu_check_batch of that header) and the results stored as
 // fuse_batch.hip stores them; and the three entry points the single-keyframe ORBmatcher::Fuse members call (sivo_mframe_create,
 // sivo_mframe_destroy, sivo_fuse), so that the adapter's program can run the loop of single calls beside the batch.  The candidate scan
-// is a plain sequential loop over Frame::GetFeaturesInArea's order in place of the wave: no library, no device, so the programs that
+// is a plain sequential loop over Frame::GetFeaturesInArea's order in place of the wave, over the grid, the window and the chi-square
+// gate of sivo_amd/csrc/grid_math.hpp (the functions the kernels run): no library, no device, so the programs that
 // include it (tests/fuse_batch_prog.cpp, tests/fuse_batch_adapter_prog.cpp) can run under the sanitizers.
 #pragma once
 #include <climits>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "fuse_math.hpp"
+#include "grid_math.hpp"
 
 // A frame handle on the host: copies of the arrays and the 64 x 48 grid in mGrid[ix][iy] order (Frame.cc:205-221, :392-404).
 struct sivo_mframe {
@@ -24,7 +26,7 @@ struct sivo_mframe {
 };
 
 namespace fuse_batch_host {
-enum { COLS = 64, ROWS = 48, TH_LOW = 50 };
+enum { ROWS = SIVO_GRID_ROWS, TH_LOW = 50 };
 inline std::string &error() { static std::string e; return e; }
 inline int fail(const char *where, const char *what) { error() = std::string(where) + ": " + what; return SIVO_ERR_INVALID_ARGUMENT; }
 struct Counters { long batch = 0, single = 0, frames_alive = 0; };
@@ -32,19 +34,13 @@ inline Counters &counters() { static Counters c; return c; }        // how many 
 
 inline void features_in_area(const sivo_mframe &F, float x, float y, float r, std::vector<int32_t> &out) {
     out.clear();
-    const int c0 = std::max(0, (int)std::floor((x - F.min_x - r) * F.inv_w));
-    if (c0 >= COLS) return;
-    const int c1 = std::min(COLS - 1, (int)std::ceil((x - F.min_x + r) * F.inv_w));
-    if (c1 < 0) return;
-    const int r0 = std::max(0, (int)std::floor((y - F.min_y - r) * F.inv_h));
-    if (r0 >= ROWS) return;
-    const int r1 = std::min(ROWS - 1, (int)std::ceil((y - F.min_y + r) * F.inv_h));
-    if (r1 < 0) return;
+    int c0, c1, r0, r1;
+    if (!sivo::grid_window(F.min_x, F.min_y, F.inv_w, F.inv_h, x, y, r, c0, c1, r0, r1)) return;
     for (int ix = c0; ix <= c1; ++ix)
         for (int iy = r0; iy <= r1; ++iy)
             for (int j = F.cell_off[(size_t)(ix * ROWS + iy)]; j < F.cell_off[(size_t)(ix * ROWS + iy + 1)]; ++j) {
                 const SivoKeyPoint &kp = F.keys[(size_t)F.cell_idx[(size_t)j]];
-                if (std::fabs(kp.x - x) < r && std::fabs(kp.y - y) < r) out.push_back(F.cell_idx[(size_t)j]);
+                if (sivo::in_window(kp.x, kp.y, x, y, r)) out.push_back(F.cell_idx[(size_t)j]);
             }
 }
 
@@ -67,15 +63,7 @@ inline void scan(const sivo_mframe &F, float u, float v, float ur, int level, co
         if (kp.octave < level - 1 || kp.octave > level) continue;
         if (!scw_variant) {
             const float kur = F.u_right.empty() ? -1.0f : F.u_right[(size_t)i];
-            const float ex = u - kp.x, ey = v - kp.y;
-            if (kur >= 0) {
-                const float er = ur - kur;
-                const float e2 = ex * ex + ey * ey + er * er;
-                if (e2 * F.inv_sigma2[(size_t)kp.octave] > 7.8) continue;
-            } else {
-                const float e2 = ex * ex + ey * ey;
-                if (e2 * F.inv_sigma2[(size_t)kp.octave] > 5.99) continue;
-            }
+            if (!sivo::fuse_chi2_gate(u - kp.x, v - kp.y, kur >= 0, ur - kur, F.inv_sigma2[(size_t)kp.octave])) continue;
         }
         const int d = hamming(desc, F.desc.data() + 32 * (size_t)i);
         if (d < best_dist) { best_dist = d; best = i; }
@@ -96,27 +84,14 @@ int sivo_mframe_create(const SivoKeyPoint *keys, int n, const float *u_right, co
     sivo_mframe *F = new sivo_mframe;
     F->device = device < 0 ? 0 : device; F->n = n; F->nlevels = nlevels;
     F->min_x = min_x; F->max_x = max_x; F->min_y = min_y; F->max_y = max_y;
-    F->inv_w = (float)COLS / (max_x - min_x);
-    F->inv_h = (float)ROWS / (max_y - min_y);
+    F->inv_w = (float)SIVO_GRID_COLS / (max_x - min_x);
+    F->inv_h = (float)SIVO_GRID_ROWS / (max_y - min_y);
     if (n) F->keys.assign(keys, keys + n);
     if (u_right && n) F->u_right.assign(u_right, u_right + n);
     if (n) F->desc.assign(descriptors, descriptors + 32 * (size_t)n);
     F->scale.assign(scale_factors, scale_factors + nlevels);
     F->inv_sigma2.assign(inv_level_sigma2, inv_level_sigma2 + nlevels);
-    const int cells = COLS * ROWS;
-    std::vector<int32_t> cell_of((size_t)n, -1);
-    F->cell_off.assign((size_t)cells + 1, 0);
-    for (int i = 0; i < n; ++i) {
-        const int px = (int)std::round((keys[i].x - min_x) * F->inv_w), py = (int)std::round((keys[i].y - min_y) * F->inv_h);
-        if (px < 0 || px >= COLS || py < 0 || py >= ROWS) continue;
-        cell_of[(size_t)i] = px * ROWS + py;
-        ++F->cell_off[(size_t)cell_of[(size_t)i] + 1];
-    }
-    for (int c = 0; c < cells; ++c) F->cell_off[(size_t)c + 1] += F->cell_off[(size_t)c];
-    F->cell_idx.assign((size_t)F->cell_off[(size_t)cells], 0);
-    std::vector<int32_t> fill(F->cell_off.begin(), F->cell_off.end() - 1);
-    for (int i = 0; i < n; ++i)
-        if (cell_of[(size_t)i] >= 0) F->cell_idx[(size_t)fill[(size_t)cell_of[(size_t)i]]++] = i;
+    sivo::grid_build(keys, n, min_x, min_y, F->inv_w, F->inv_h, F->cell_off, F->cell_idx);
     ++counters().frames_alive;
     *out = F;
     return SIVO_OK;

@@ -210,3 +210,116 @@ def test_empty_inputs(scene):
     nm, match, _ = M.search_by_projection_frame(empty, np.ones(len(u), np.uint8), u, v, inv_z, octave, angle, desc, obs, 7.0, False, False,
                                                 BF, True, np.zeros(0, np.int32))
     assert nm == 0 and len(match) == 0
+
+
+# ---- the window walk at its edges ------------------------------------------------------------------------------------------------------
+# A 640 x 480 frame: cells of 10 x 10 px, cell (cx, cy) holding the keys whose x * 0.1 and y * 0.1 ROUND to (cx, cy).  70 keys in each of
+# the cells (20, 20) and (21, 20): a grid column's span is longer than the 64 lanes.  Two keys in a cell at each border of the grid and one
+# key right of the last column's centre band, which belongs to no cell.  Every key has one descriptor, every query the same one three
+# bits off: all candidates tie at distance 3 and the visiting order alone decides.
+WIN_BOUNDS = (0.0, 640.0, 0.0, 480.0)
+WIN_LEFT, WIN_RIGHT, WIN_TOP, WIN_BOTTOM, WIN_NO_CELL = (0, 1), (2, 3), (4, 5), (6, 7), 8
+
+
+def window_scene():
+    rng = np.random.default_rng(77)
+    border = [(2.0, 240.0), (3.0, 241.0), (634.5, 240.0), (633.0, 241.0), (320.0, 2.0), (321.0, 3.0), (320.0, 474.0), (321.0, 473.0),
+              (637.0, 240.0)]
+    j = np.arange(70)
+    cell_a = np.stack([195.5 + (j % 10) * 0.9, 195.5 + (j // 10) * 1.2], 1)
+    dense = np.concatenate([cell_a, cell_a + (10.0, 0.0)])
+    perm = rng.permutation(140)                                   # the key indices of the two cells interleave
+    xy = np.concatenate([np.array(border), dense[perm]]).astype(np.float32)
+    in_a = np.flatnonzero(np.concatenate([np.zeros(9, bool), perm < 70]))
+    in_b = np.flatnonzero(np.concatenate([np.zeros(9, bool), perm >= 70]))
+    keys = np.zeros(len(xy), M.KP_DTYPE)
+    keys["x"], keys["y"], keys["size"] = xy[:, 0], xy[:, 1], 31.0
+    desc = np.repeat(rng.integers(0, 256, (1, 32), dtype=np.uint8), len(xy), 0)
+    qdesc = desc[0].copy(); qdesc[[0, 13, 31]] ^= np.uint8(0x10)
+    scale = (1.2 ** np.arange(8)).astype(np.float32)
+    tabs = (scale, scale * scale, (1.0 / (scale * scale)).astype(np.float32))
+    # (name, u, v, radius, first candidate of GetFeaturesInArea's walk, last candidate, number of candidates); None: no candidate
+    A = xy[in_a]
+    inside = in_a[(np.abs(A[:, 0] - 200.0) < 4.0) & (np.abs(A[:, 1] - 200.0) < 4.0)]
+    queries = [("inside one cell", 200.0, 200.0, 4.0, inside.min(), inside.max(), len(inside)),
+               ("both cells", 205.0, 199.0, 12.0, in_a.min(), in_b.max(), 140),
+               ("left of the grid", -30.0, 240.0, 4.0, None, None, 0),
+               ("right of the grid", 680.0, 240.0, 4.0, None, None, 0),
+               ("above the grid", 320.0, -30.0, 4.0, None, None, 0),
+               ("below the grid", 320.0, 520.0, 4.0, None, None, 0),
+               ("clamped left", 1.0, 240.0, 4.0, WIN_LEFT[0], WIN_LEFT[1], 2),
+               ("clamped right", 638.0, 240.0, 4.0, WIN_RIGHT[0], WIN_RIGHT[0], 1),     # (633, 241) is 5 px away, 637 is in no cell
+               ("clamped top", 320.0, 1.0, 4.0, WIN_TOP[0], WIN_TOP[1], 2),
+               ("clamped bottom", 320.0, 477.0, 4.0, WIN_BOTTOM[0], WIN_BOTTOM[0], 1),  # (321, 473) is 4 px away: not < r
+               ("the whole image", 320.0, 240.0, 700.0, WIN_LEFT[0], WIN_RIGHT[1], len(xy) - 1)]
+    return dict(keys=keys, desc=desc, qdesc=qdesc, tabs=tabs, queries=queries)
+
+
+def window_expectations(s, oracle_frame):
+    """What the CPU checkers say of the scene, with the outcomes it was built for asserted (so no comparison below is vacuous): per query
+    the pick with the first and with the last minimum winning (the search oracle's GetFeaturesInArea), and, per radius, the restatement
+    of sivo_fuse_batch for a one-keyframe camera under which point i projects to query i's (u, v)."""
+    import fuse_batch_restatement as R
+    F32 = np.float32
+    first, last = [], []
+    for name, u, v, r, want_first, want_last, count in s["queries"]:
+        cand = oracle_frame.features_in_area(u, v, r)
+        assert len(cand) == count and WIN_NO_CELL not in cand, name
+        assert (cand[0], cand[-1]) == (want_first, want_last) if count else want_first is None, name
+        first.append(cand[0] if count else -1); last.append(cand[-1] if count else -1)
+    first, last = np.array(first, np.int32), np.array(last, np.int32)
+    nq = len(first)
+    u, v, r = (np.array([q[i] for q in s["queries"]], F32) for i in (1, 2, 3))
+    valid = np.ones(nq, np.uint8); lvl0 = np.zeros(nq, np.int32)
+    qd = np.repeat(s["qdesc"][None], nq, 0)
+    for rad in np.unique(r):                                      # the oracle's Fuse agrees on the first minimum and its distance
+        sel = r == rad
+        _, bi, bd = OS.fuse(oracle_frame, valid[sel], u[sel], v[sel], None, lvl0[sel], qd[sel], float(rad), 1)
+        assert np.array_equal(bi, first[sel]) and np.array_equal(bd[bi >= 0], np.full((bi >= 0).sum(), 3))
+    # identity pose, fx = fy = 1, cx = cy = 0, the point at (u, v, 1): x * (1 / 1) * 1 + 0 is u to the bit; maxDist = dist: level 0
+    pos = np.stack([u, v, np.ones(nq, F32)], 1)
+    dist = np.sqrt((pos.astype(np.float64) ** 2).sum(1)).astype(F32)
+    normal = (pos / dist[:, None]).astype(F32)
+    cam = np.zeros(1, R.CAMERA_DTYPE)
+    cam["Rcw"][0] = np.eye(3, dtype=F32).ravel()
+    cam["fx"], cam["fy"], cam["bf"] = 1.0, 1.0, 40.0
+    cam["min_x"], cam["max_x"], cam["min_y"], cam["max_y"] = -100.0, 800.0, -100.0, 600.0       # wider than the grid: a window can miss it
+    cam["log_scale_factor"], cam["nlevels"] = np.log(F32(1.2)), 8
+    k = s["keys"]
+    frame = R.Frame(k["x"], k["y"], k["octave"], None, s["desc"], WIN_BOUNDS, s["tabs"][0], s["tabs"][2])
+    batch = {}
+    for scw in (1, 0):
+        cam["scw_variant"] = scw
+        for rad in np.unique(r):
+            sel = np.flatnonzero(r == rad)
+            want = R.fuse_batch([frame], cam, pos[sel], normal[sel], F32(0.5) * dist[sel], dist[sel], qd[sel], float(rad))
+            assert np.array_equal(want["u"][0], u[sel]) and np.array_equal(want["v"][0], v[sel]) and (want["level"] == 0).all()
+            if scw:                                               # without the chi-square gate the batch is the first-minimum search
+                assert np.array_equal(want["best_idx"][0], first[sel])
+                assert np.array_equal(want["status"][0], np.where(first[sel] >= 0, R.MATCHED, R.NO_CANDIDATE))
+            batch[scw, float(rad)] = (sel, cam.copy(), (pos[sel], normal[sel], F32(0.5) * dist[sel], dist[sel], qd[sel]), want)
+    return first, last, batch
+
+
+def test_window_walk_at_the_cell_and_grid_edges():
+    """scan_window, shared by search_round_kernel and fuse_batch_kernel: a span longer than the wave, a walk over two columns with every
+    candidate tied, windows that miss the grid on each side, windows clamped at each border, a window over the whole grid."""
+    s = window_scene()
+    Fo = OS.Frame(s["keys"], None, s["desc"], WIN_BOUNDS, *s["tabs"])
+    Fg = M.MatchFrame(s["keys"], None, s["desc"], WIN_BOUNDS, *s["tabs"])
+    first, last, batch = window_expectations(s, Fo)
+    nq = len(first)
+    q = np.zeros(nq, M.QUERY_DTYPE)
+    q["u"], q["v"], q["radius"] = ([x[i] for x in s["queries"]] for i in (1, 2, 3))
+    q["lvl_lo"], q["lvl_hi"], q["flags"] = -1, 0, M.Q_VALID
+    qd = np.repeat(s["qdesc"][None], nq, 0)
+    for tie_last, want in ((0, first), (1, last)):
+        r = M.search(Fg, q, qd, dict(th_dist=50, tie_last=tie_last))
+        assert np.array_equal(r["match_query"], want), tie_last
+        assert np.array_equal(r["best_dist"], np.where(want >= 0, 3, 256)) and r["n_matches"] == (want >= 0).sum()
+    for (scw, rad), (sel, cam, args, want) in batch.items():
+        got = M.fuse_batch([Fg], cam, *args, rad)
+        for k in ("best_idx", "best_dist", "status", "level"):
+            assert np.array_equal(got[k], want[k]), (scw, rad, k)
+        for k in ("u", "v", "ur"):
+            assert got[k].tobytes() == want[k].tobytes(), (scw, rad, k)
