@@ -587,6 +587,44 @@ int sivo_local_ba(double *poses, const uint8_t *pose_fixed, int n_poses, double 
                   const SivoEdge *edges, int64_t n_edges, const double intr[5], const volatile uint8_t *stop_flag,
                   uint8_t *outlier, int cov_pose, double *cov, int *cov_ok, int *iterations, int *trials);
 
+/* How the reduced camera system of a bundle adjustment is solved.  DENSE: a dense
+ * (free pose x point) edge table, one workgroup per keyframe pair, a dense Cholesky
+ * — the form of the local BA; refuses n_free * n_points > 2^28.  SPARSE: S holds
+ * the blocks of keyframe pairs that share a point, is assembled from per-block
+ * contribution lists and factored by a 6 x 6 block sparse Cholesky over a host
+ * plan (minimum-degree order, elimination-tree levels) — the form of the global
+ * BA.  AUTO: SPARSE when DENSE would refuse the problem or from 64 free keyframes
+ * on, DENSE otherwise.  Zero-initialise, set size = sizeof(SivoBaOptions); NULL
+ * means AUTO.  The library reads no environment variable. */
+#define SIVO_BA_SOLVER_AUTO 0
+#define SIVO_BA_SOLVER_DENSE 1
+#define SIVO_BA_SOLVER_SPARSE 2
+typedef struct SivoBaOptions {
+    uint32_t size;               /* sizeof(SivoBaOptions) of the caller's header */
+    int32_t solver;              /* SIVO_BA_SOLVER_* */
+} SivoBaOptions;
+
+/* sivo_ba_optimize / sivo_local_ba with options (NULL: the plain functions). */
+int sivo_ba_optimize_opts(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
+                          const SivoEdge *edges, int64_t n_edges, const double intr[5], double delta_mono,
+                          double delta_stereo, const uint8_t *level, const uint8_t *robust, int iterations,
+                          const volatile uint8_t *stop_flag, double *err_out, double *hpp_last_out,
+                          int *iterations_run, int *trials, const SivoBaOptions *opts);
+int sivo_local_ba_opts(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
+                       const SivoEdge *edges, int64_t n_edges, const double intr[5], const volatile uint8_t *stop_flag,
+                       uint8_t *outlier, int cov_pose, double *cov, int *cov_ok, int *iterations, int *trials,
+                       const SivoBaOptions *opts);
+
+/* What the host prepares for the sparse path of a problem, without touching a
+ * device: out[0] free poses, [1] blocks of S below the diagonal, [2] off-diagonal
+ * blocks of L, [3] nnz(L) in scalars (lower triangle), [4] flops of one numeric
+ * factorisation, [5] levels of the elimination tree, [6] contribution pairs,
+ * [7] the path `opts` takes (1 dense, 2 sparse).  An index out of range, two
+ * edges on one (keyframe, map point) pair, a NULL array with a non-zero count, or
+ * DENSE on a problem the dense path refuses -> SIVO_ERR_INVALID_ARGUMENT. */
+int sivo_ba_analyze(const uint8_t *pose_fixed, int n_poses, int n_points, const SivoEdge *edges, int64_t n_edges,
+                    const SivoBaOptions *opts, int64_t out[8]);
+
 /* Optimizer::PoseOptimization from the point the edges are built
  * (Optimizer.cc:409-491): 4 rounds of optimize(10) from the initial pose, chi2
  * test (7.815) on the STEREO edges after each round — the reference never

@@ -44,6 +44,10 @@ class SegnetOptions(C.Structure):   # == SivoSegnetOptions
                 ("no_packed_activations", C.c_int32), ("conv7_fp32", C.c_int32), ("wino4_workspace_mb", C.c_int32), ("debug_sync", C.c_int32)]
 
 
+class BaOptions(C.Structure):   # == SivoBaOptions
+    _fields_ = [("size", C.c_uint32), ("solver", C.c_int32)]
+
+
 class SearchQuery(C.Structure):   # == SivoSearchQuery (36 bytes)
     _fields_ = [("u", C.c_float), ("v", C.c_float), ("radius", C.c_float), ("lvl_lo", C.c_int32), ("lvl_hi", C.c_int32),
                 ("ur", C.c_float), ("gate", C.c_float), ("angle", C.c_float), ("flags", C.c_int32)]
@@ -210,6 +214,9 @@ SIGNATURES = {
     "sivo_check_semantics": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(_d), _d, _d, _d, _vp, _i, _d, _d, _vp, _vp, _vp],
     "sivo_ba_optimize": [_vp, _vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _d, _d, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_local_ba": [_vp, _vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _vp, _vp, _i, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    "sivo_ba_optimize_opts": [_vp, _vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _d, _d, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), _vp],
+    "sivo_local_ba_opts": [_vp, _vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _vp, _vp, _i, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp],
+    "sivo_ba_analyze": [_vp, _i, _i, _vp, _i64, _vp, _vp],
     "sivo_pose_optimize": [_vp, _vp, _i, _vp, _i64, C.POINTER(_d), _vp, _vp, _vp, C.POINTER(_i), _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "sivo_sim3_optimize": [_vp, C.POINTER(_d), C.POINTER(_d), _vp, _i, _f, _i, _vp, C.POINTER(_i), _vp, _vp, C.POINTER(_i), C.POINTER(_i)],
     "sivo_sim3_optimize_batch": [_vp, _i],

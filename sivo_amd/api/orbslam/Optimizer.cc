@@ -41,6 +41,11 @@ static_assert(sizeof(bool) == 1, "pbStopFlag is handed to the C ABI as a byte");
 const volatile uint8_t *stop_byte(const bool *p) { return reinterpret_cast<const volatile uint8_t *>(p); }
 }  // namespace
 
+// The entry points with options are referenced weakly: a program that links this file against an implementation of the C ABI without
+// them (the plain entry points are all the default path needs) still links, and is told so if it passes options.
+#pragma weak sivo_ba_optimize_opts
+#pragma weak sivo_local_ba_opts
+
 int Optimizer::PoseOptimization(double pose[12], const std::vector<double> &mapPoints, const std::vector<SivoEdge> &edges,
                                 const double intr[5], std::vector<uint8_t> &outlier, double covariance[36],
                                 bool *covarianceValid) {
@@ -59,14 +64,21 @@ int Optimizer::PoseOptimization(double pose[12], const std::vector<double> &mapP
 void Optimizer::LocalBundleAdjustment(std::vector<double> &poses, const std::vector<uint8_t> &fixedPose,
                                       std::vector<double> &points, const std::vector<SivoEdge> &edges, const double intr[5],
                                       const bool *pbStopFlag, std::vector<uint8_t> &erase, int covariancePose,
-                                      double *covariance, bool *covarianceValid) {
+                                      double *covariance, bool *covarianceValid, const SivoBaOptions *options) {
     if (fixedPose.size() * 12 != poses.size()) throw std::invalid_argument("fixedPose must hold one flag per keyframe");
     erase.assign(edges.size(), 0);
     double cov[36];
     int ok = 0;
-    raise(sivo_local_ba(poses.data(), fixedPose.data(), (int)fixedPose.size(), points.data(), (int)(points.size() / 3),
-                        edges.data(), (int64_t)edges.size(), intr, stop_byte(pbStopFlag), erase.data(),
-                        covariancePose, cov, &ok, nullptr, nullptr));
+    if (!options) {
+        raise(sivo_local_ba(poses.data(), fixedPose.data(), (int)fixedPose.size(), points.data(), (int)(points.size() / 3),
+                            edges.data(), (int64_t)edges.size(), intr, stop_byte(pbStopFlag), erase.data(),
+                            covariancePose, cov, &ok, nullptr, nullptr));
+    } else {
+        if (!sivo_local_ba_opts) throw std::runtime_error("the C ABI linked here has no sivo_local_ba_opts");
+        raise(sivo_local_ba_opts(poses.data(), fixedPose.data(), (int)fixedPose.size(), points.data(), (int)(points.size() / 3),
+                                 edges.data(), (int64_t)edges.size(), intr, stop_byte(pbStopFlag), erase.data(),
+                                 covariancePose, cov, &ok, nullptr, nullptr, options));
+    }
     if (ok && covariance)
         for (int i = 0; i < 36; ++i) covariance[i] = cov[i];
     if (covarianceValid) *covarianceValid = ok != 0;
@@ -74,13 +86,21 @@ void Optimizer::LocalBundleAdjustment(std::vector<double> &poses, const std::vec
 
 void Optimizer::BundleAdjustment(std::vector<double> &poses, const std::vector<uint8_t> &fixedPose, std::vector<double> &points,
                                  const std::vector<SivoEdge> &edges, const double intr[5], int nIterations,
-                                 const bool *pbStopFlag, bool bRobust) {
+                                 const bool *pbStopFlag, bool bRobust, const SivoBaOptions *options) {
     if (fixedPose.size() * 12 != poses.size()) throw std::invalid_argument("fixedPose must hold one flag per keyframe");
     const std::vector<uint8_t> robust(edges.size(), bRobust ? 1 : 0);
-    raise(sivo_ba_optimize(poses.data(), fixedPose.data(), (int)fixedPose.size(), points.data(), (int)(points.size() / 3),
-                           edges.data(), (int64_t)edges.size(), intr, (double)std::sqrt(5.991f), (double)std::sqrt(7.815f),   // :133-134
-                           nullptr, robust.data(), nIterations, stop_byte(pbStopFlag), nullptr, nullptr, nullptr,
-                           nullptr));
+    if (!options) {
+        raise(sivo_ba_optimize(poses.data(), fixedPose.data(), (int)fixedPose.size(), points.data(), (int)(points.size() / 3),
+                               edges.data(), (int64_t)edges.size(), intr, (double)std::sqrt(5.991f), (double)std::sqrt(7.815f),   // :133-134
+                               nullptr, robust.data(), nIterations, stop_byte(pbStopFlag), nullptr, nullptr, nullptr,
+                               nullptr));
+    } else {
+        if (!sivo_ba_optimize_opts) throw std::runtime_error("the C ABI linked here has no sivo_ba_optimize_opts");
+        raise(sivo_ba_optimize_opts(poses.data(), fixedPose.data(), (int)fixedPose.size(), points.data(), (int)(points.size() / 3),
+                                    edges.data(), (int64_t)edges.size(), intr, (double)std::sqrt(5.991f), (double)std::sqrt(7.815f),
+                                    nullptr, robust.data(), nIterations, stop_byte(pbStopFlag), nullptr, nullptr, nullptr,
+                                    nullptr, options));
+    }
 }
 
 }  // namespace SIVO

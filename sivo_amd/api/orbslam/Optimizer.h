@@ -50,17 +50,19 @@ class Optimizer {
     // void Optimizer::LocalBundleAdjustment(KeyFrame*, bool *pbStopFlag, Map*, bool) (Optimizer.cc:493-926) from the
     // built graph on: poses (fixedPose[i] != 0 for lFixedCameras and keyframe 0) and points are optimised in place;
     // erase[e] = 1 for the observations the caller removes (:824-878); covariance = marginal block of keyframe
-    // covariancePose (:900-907).
+    // covariancePose (:900-907).  options: how the reduced camera system is solved (SivoBaOptions, include/sivo_hip.h); nullptr = AUTO:
+    // the dense path below 64 free keyframes, the sparse one from there on or when the dense edge table would be refused.
     static void LocalBundleAdjustment(std::vector<double> &poses, const std::vector<uint8_t> &fixedPose,
                                       std::vector<double> &points, const std::vector<SivoEdge> &edges, const double intr[5],
                                       const bool *pbStopFlag, std::vector<uint8_t> &erase, int covariancePose = -1,
-                                      double *covariance = nullptr, bool *covarianceValid = nullptr);
+                                      double *covariance = nullptr, bool *covarianceValid = nullptr, const SivoBaOptions *options = nullptr);
 
     // void Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust) (Optimizer.cc:49-271)
-    // from the built graph on: one optimize(nIterations) with (bRobust) or without Huber kernels.
+    // from the built graph on: one optimize(nIterations) with (bRobust) or without Huber kernels.  GlobalBundleAdjustment(Map *, ...)
+    // comes through here with options = nullptr: a map of loop-closing size takes the sparse path.
     static void BundleAdjustment(std::vector<double> &poses, const std::vector<uint8_t> &fixedPose, std::vector<double> &points,
                                  const std::vector<SivoEdge> &edges, const double intr[5], int nIterations = 5,
-                                 const bool *pbStopFlag = nullptr, bool bRobust = true);
+                                 const bool *pbStopFlag = nullptr, bool bRobust = true, const SivoBaOptions *options = nullptr);
 
     // ---- the reference's own static members over the SLAM object graph (reference include/orbslam/Optimizer.h:46-60), so
     // that its callers compile against this class as they are: Tracking.cc:617,753,792,1329 `Optimizer::PoseOptimization(

@@ -11,9 +11,15 @@
 //   poses 12/keyframe (Rcw row-major, tcw), points 3/map point, SivoEdge 48 B/edge;
 //   per edge:  err 3, Jp 18, Jx 9, W = w*Omega*Jp'Jx 18, Y = W*Hll^-1 18;
 //   per point: Hll 9, bl 3, Hll^-1 9, dx 3;   per free pose: Hpp 36, bp 6;
-//   reduced system S (6F x 6F, dense) + rhs; CSR edge lists by point and by free pose; a dense
-//   (free pose x point) -> edge table that turns the Schur products into gathers with a fixed
-//   summation order (no atomics: results are reproducible run to run).
+//   CSR edge lists by point and by free pose; the reduced system S + rhs on one of two paths (SivoBaOptions.solver; AUTO = dense
+//   below 64 free keyframes, sparse from there on or when the dense table would be refused):
+//   dense  (the local BA): S 6F x 6F; a dense (free pose x point) -> edge table that turns the Schur products into gathers
+//          with a fixed summation order; one workgroup per keyframe pair; a dense blocked Cholesky in one workgroup;
+//   sparse (the global BA; measured 7.2 ms against 1458 ms per call at 512 free keyframes): 36 doubles per block of L
+//          in the host's block order — diagonal blocks first, a block of S where the two keyframes share a point, fill blocks zero —
+//          written by one owner wave per block from its (edge, edge) contribution list, factored level by level over the host
+//          plan (ba_sparse_plan.hpp, sparse_plan.hpp) by one workgroup; neither the table nor the dense S exists there.
+//   No atomics on either path: results are reproducible run to run.
 //
 // Pose-only problems (one vertex, <= a few thousand edges) run the WHOLE schedule — 4 rounds x 10
 // LM iterations x up to 10 trials, the chi2 re-classification and the covariance — in ONE launch of a
@@ -35,6 +41,9 @@
 #include "solver_host.hpp"
 
 #pragma clang fp contract(off)
+
+#include "ba_sparse_math.hpp"
+#include "ba_sparse_plan.hpp"
 
 namespace sivo {
 
@@ -817,15 +826,7 @@ __global__ __launch_bounds__(1024) void ba_maxdiag_kernel(BaDev d, int with_poin
 // (Hll_q + lambda I)^-1 — formed where it is used (every edge of the point, and the point's update) instead of by a launch of
 // its own: 9 loads and ~40 flops
 __device__ __forceinline__ void ba_point_inverse(const BaDev &d, int q, double lambda, double (&Ai)[9]) {
-    double A[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) A[i] = d.Hll[9 * (int64_t)q + i];
-    A[0] += lambda; A[4] += lambda; A[8] += lambda;
-    const double c0 = A[4] * A[8] - A[5] * A[7], c1 = A[5] * A[6] - A[3] * A[8], c2 = A[3] * A[7] - A[4] * A[6];
-    const double det = A[0] * c0 + A[1] * c1 + A[2] * c2, id = 1.0 / det;
-    Ai[0] = c0 * id; Ai[1] = (A[2] * A[7] - A[1] * A[8]) * id; Ai[2] = (A[1] * A[5] - A[2] * A[4]) * id;
-    Ai[3] = c1 * id; Ai[4] = (A[0] * A[8] - A[2] * A[6]) * id; Ai[5] = (A[2] * A[3] - A[0] * A[5]) * id;
-    Ai[6] = c2 * id; Ai[7] = (A[1] * A[6] - A[0] * A[7]) * id; Ai[8] = (A[0] * A[4] - A[1] * A[3]) * id;
+    bs_point_inverse(d.Hll + 9 * (int64_t)q, lambda, Ai);           // (ba_sparse_math.hpp: the host program of the tests forms it with the same code)
 }
 
 // S block (i, j), i <= j:  [i == j] (Hpp_i + lambda I)  -  sum_q Y_{e(i,q)} W_{e(j,q)}' ; rhs_i = bp_i - sum_q Y_{e(i,q)} bl_q
@@ -1145,6 +1146,162 @@ __global__ __launch_bounds__(BA_SOLVE_T) void ba_dense_solve_lds_kernel(BaDev d)
     if (tid == 0) d.scal[3] = ok ? 1.0 : 0.0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The sparse path of the reduced camera system (a global bundle adjustment: hundreds to thousands of free keyframes, each sharing
+// points with a few dozen others).  The host plans once per BaSolver (ba_sparse_plan.hpp): the blocks of S, a minimum-degree order,
+// the blocks of L with their update lists, the levels of the elimination tree, and per owner block of S the (edge, edge) pairs through a
+// common point in increasing point order.  Two launches replace ba_schur_kernel and ba_dense_solve_*; nothing dense is allocated.
+// One owner per block, host-fixed order of every sum, no floating-point atomics: bit-identical run to run.
+// ------------------------------------------------------------------------------------------------
+struct BaSparseDev {
+    const int32_t *own_blk, *con_ptr, *con;    // owner -> L block; CSR of its contribution pairs: (edge of the row pose, edge of the column pose)
+    const int32_t *perm;                       // elimination position -> free slot
+    double *H;                                 // 36 per L block: S + lambda I in the factor's block order (the fill blocks stay zero)
+    double *b;                                 // 6 per position: the right-hand side
+    double *L, *rinv, *x;                      // 36 per L block; 6 per position: 1 / L_pp[r][r]; 6 per position: y, then the solution
+    const int32_t *lvl_ptr, *lvl_col, *off_ptr, *off_blk, *blk_col, *pair_ptr, *pairs, *row_ptr, *row_lst, *col_ptr, *col_lst;
+    int na, nlev, n_own;
+};
+
+// S block by block: ONE wave per owner block, lane 6 r + c of entry (r, c), lanes 36 .. 41 of the right-hand side (diagonal owners).
+//   S_ij = [i == j] (Hpp_i + lambda I) - sum_q Y_{e(i,q)} W_{e(j,q)}'      rhs_i = bp_i - sum_q Y_{e(i,q)} bl_q
+// over the block's contribution list only, pairs in the host's order (increasing point index); Y = W (Hll_q + lambda I)^-1 is formed
+// here, as in ba_schur_kernel, and the level test on both edges is the same.  The block is written where the factorisation reads it.
+constexpr int BA_SP_T = 256;
+__global__ __launch_bounds__(BA_SP_T) void ba_sparse_schur_kernel(BaDev d, BaSparseDev s) {
+    if (ba_lm_idle(d)) return;
+    const int o = blockIdx.x * (BA_SP_T / 64) + (threadIdx.x >> 6);
+    if (o >= s.n_own) return;
+    const double *Wc = ba_set(d, __builtin_amdgcn_readfirstlane(d.lm->cur)).W;
+    const double lambda = d.lm->lambda;
+    const int lane = threadIdx.x & 63;
+    const int blk = s.own_blk[o];
+    const bool diag = blk < s.na, ent = lane < 36, rhs = diag && lane >= 36 && lane < 42;
+    const int r = ent ? lane / 6 : rhs ? lane - 36 : 0, c = ent ? lane % 6 : 0;
+    double acc = 0.0;
+#pragma unroll 2                                 // (the loads of the next pair issue ahead; the additions stay in list order)
+    for (int64_t q = s.con_ptr[o]; q < s.con_ptr[o + 1]; ++q) {
+        const int e1 = s.con[2 * q], e2 = s.con[2 * q + 1];
+        if (d.level[e1] || d.level[e2]) continue;
+        const int pt = d.edges[e1].point;
+        double Ai[9], y[3];
+        ba_point_inverse(d, pt, lambda, Ai);
+        bs_y_row(Wc + 18 * (int64_t)e1 + 3 * r, Ai, y);
+        acc += bs_contrib(y, rhs ? d.bl + 3 * (int64_t)pt : Wc + 18 * (int64_t)e2 + 3 * c);
+    }
+    if (ent) {
+        double v = -acc;
+        if (diag) { v += d.Hpp[36 * (int64_t)s.perm[blk] + lane]; if (r == c) v += lambda; }
+        s.H[(int64_t)blk * 36 + lane] = v;
+    } else if (rhs) {
+        s.b[(int64_t)blk * 6 + r] = d.bp[6 * (int64_t)s.perm[blk] + r] - acc;
+    }
+}
+
+// v = sum over the block pairs of (L_ik L_jk^T)[r][c], pairs in the host's order
+__device__ __forceinline__ double ba_sparse_pair_sum(const BaSparseDev &s, int blk, int r, int c) {
+    double acc = 0.0;
+#pragma unroll 4
+    for (int q = s.pair_ptr[blk]; q < s.pair_ptr[blk + 1]; ++q)
+        acc += bs_dot6(s.L + (int64_t)s.pairs[2 * (int64_t)q] * 36 + 6 * r, s.L + (int64_t)s.pairs[2 * (int64_t)q + 1] * 36 + 6 * c);
+    return acc;
+}
+
+// 6 x 6 block sparse Cholesky of S and the two triangular solves, left-looking, level by level over the plan, in ONE workgroup (the
+// barrier between levels is __syncthreads: no cooperative launch, no grid-wide wait).  One wave per block of a level, every lane of the
+// wave holds the whole block after a shuffle (eg_factor_solve_kernel is the model).  The increments leave in slot order (xs);
+// scal[3] = 1 on success, 0 when a pivot is not positive — the rule of ba_dense_solve_kernel's s_ok.
+constexpr int BA_SF_T = 1024;
+__global__ __launch_bounds__(BA_SF_T) void ba_sparse_solve_kernel(BaDev d, BaSparseDev s) {
+    if (ba_lm_idle(d)) return;
+    __shared__ int s_fail;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int NW = BA_SF_T / 64;
+    const int r = lane < 36 ? lane / 6 : 0, c = lane < 36 ? lane % 6 : 0;
+    if (threadIdx.x == 0) s_fail = 0;
+    __syncthreads();
+    for (int lv = 0; lv < s.nlev; ++lv) {
+        for (int t = s.lvl_ptr[lv] + wave; t < s.lvl_ptr[lv + 1]; t += NW) {            // diagonal blocks of the level's columns
+            const int j = s.lvl_col[t];
+            const double v = s.H[(int64_t)j * 36 + 6 * r + c] - ba_sparse_pair_sum(s, j, r, c);
+            double A[36], rd[6];
+#pragma unroll
+            for (int k = 0; k < 36; ++k) A[k] = __shfl(v, k, 64);
+            const bool ok = bs_chol6(A, rd);
+            if (!ok && lane == 0) s_fail = 1;
+            // (every lane holds the whole factor: its own entry by a chain of selects — indexing A with the lane would put A in scratch)
+            double mine = 0.0;
+#pragma unroll
+            for (int k = 0; k < 36; ++k) mine = (lane == k && k % 6 <= k / 6) ? A[k] : mine;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) mine = lane == 36 + k ? rd[k] : mine;
+            if (lane < 36) s.L[(int64_t)j * 36 + lane] = mine;
+            else if (lane < 42) s.rinv[(int64_t)j * 6 + lane - 36] = mine;
+        }
+        __syncthreads();
+        for (int t = s.off_ptr[lv] + wave; t < s.off_ptr[lv + 1]; t += NW) {            // off-diagonal blocks: (S - sum) L_jj^-T
+            const int blk = s.off_blk[t], j = s.blk_col[blk];
+            const double v = s.H[(int64_t)blk * 36 + 6 * r + c] - ba_sparse_pair_sum(s, blk, r, c);
+            double row[6], X[6];
+#pragma unroll
+            for (int m = 0; m < 6; ++m) row[m] = __shfl(v, 6 * r + m, 64);
+            bs_panel_row(row, s.L + (int64_t)j * 36, s.rinv + (int64_t)j * 6, X);
+            double out = X[0];
+#pragma unroll
+            for (int m = 1; m < 6; ++m) out = c == m ? X[m] : out;
+            if (lane < 36) s.L[(int64_t)blk * 36 + lane] = out;
+        }
+        __syncthreads();
+    }
+    const bool ok = s_fail == 0;
+    if (ok) {
+        // L y = b, levels upwards: y_j = L_jj^-1 (b_j - sum_k L_jk y_k)
+        for (int lv = 0; lv < s.nlev; ++lv) {
+            for (int t = s.lvl_ptr[lv] + wave; t < s.lvl_ptr[lv + 1]; t += NW) {
+                const int j = s.lvl_col[t];
+                const int rr = lane < 6 ? lane : 0;
+                double a = s.b[(int64_t)j * 6 + rr];
+#pragma unroll 4
+                for (int q = s.row_ptr[j]; q < s.row_ptr[j + 1]; ++q)
+                    a -= bs_dot6(s.L + (int64_t)s.row_lst[2 * q] * 36 + 6 * rr, s.x + (int64_t)s.row_lst[2 * q + 1] * 6);
+                double sv[6], y[6];
+#pragma unroll
+                for (int m = 0; m < 6; ++m) sv[m] = __shfl(a, m, 64);
+                bs_forward6(sv, s.L + (int64_t)j * 36, s.rinv + (int64_t)j * 6, y);
+                double out = y[0];
+#pragma unroll
+                for (int m = 1; m < 6; ++m) out = rr == m ? y[m] : out;
+                if (lane < 6) s.x[(int64_t)j * 6 + lane] = out;
+            }
+            __syncthreads();
+        }
+        // L^T x = y, levels downwards: x_j = L_jj^-T (y_j - sum_i L_ij^T x_i); the increments go out in slot order
+        for (int lv = s.nlev - 1; lv >= 0; --lv) {
+            for (int t = s.lvl_ptr[lv] + wave; t < s.lvl_ptr[lv + 1]; t += NW) {
+                const int j = s.lvl_col[t];
+                const int rr = lane < 6 ? lane : 0;
+                double a = s.x[(int64_t)j * 6 + rr];
+#pragma unroll 4
+                for (int q = s.col_ptr[j]; q < s.col_ptr[j + 1]; ++q)
+                    a -= bs_dot6_col(s.L + (int64_t)s.col_lst[2 * q] * 36 + rr, s.x + (int64_t)s.col_lst[2 * q + 1] * 6);
+                double sv[6], xx[6];
+#pragma unroll
+                for (int m = 0; m < 6; ++m) sv[m] = __shfl(a, m, 64);
+                bs_backward6(sv, s.L + (int64_t)j * 36, s.rinv + (int64_t)j * 6, xx);
+                double out = xx[0];
+#pragma unroll
+                for (int m = 1; m < 6; ++m) out = rr == m ? xx[m] : out;
+                if (lane < 6) {
+                    s.x[(int64_t)j * 6 + lane] = out;
+                    d.xs[6 * (int64_t)s.perm[j] + lane] = out;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x == 0) d.scal[3] = ok ? 1.0 : 0.0;
+}
+
 // dx_l = Hll^-1 (bl - sum_e W_e' dx_p), points_trial = points + dx_l, per-point share of computeScale
 __device__ __forceinline__ void ba_point_update_body(const BaDev &d, const double *Wc, int block, double lambda, const double *points, double *points_trial) {
     const int t = block * BA_T + threadIdx.x, sub = t & (BA_PL - 1);
@@ -1311,47 +1468,47 @@ static thread_local BaStopCtx t_stop;
 class BaSolver {
  public:
     BaSolver(const double *poses, const uint8_t *fixed, int nP, const double *points, int nX, bool points_fixed,
-             const SivoEdge *edges, int64_t nE, const double intr[5], double dm, double ds)
+             const SivoEdge *edges, int64_t nE, const double intr[5], double dm, double ds, int solver = SIVO_BA_SOLVER_AUTO)
         : nP_(nP), nX_(nX), nE_(nE), points_fixed_(points_fixed) {
-        if (nP < 0 || nX < 0 || nE < 0) throw std::invalid_argument("negative size");
-        if (nE > INT32_MAX) throw std::invalid_argument("too many edges");
-        std::vector<int32_t> slot((size_t)std::max(nP, 1), -1);
-        nF_ = 0;
-        for (int i = 0; i < nP; ++i) slot[i] = fixed && fixed[i] ? -1 : nF_++;
-        for (int64_t e = 0; e < nE; ++e)
-            if (edges[e].pose < 0 || edges[e].pose >= nP || edges[e].point < 0 || edges[e].point >= nX)
-                throw std::invalid_argument("edge refers to a pose/point outside the arrays");
-        if ((int64_t)nF_ * nX > ((int64_t)1 << 28)) throw std::invalid_argument("problem too large for the dense (free pose x point) edge table");
-        // CSR by point and by free pose; (free pose, point) -> edge table
-        std::vector<int64_t> pt_off((size_t)nX + 1, 0), ps_off((size_t)nF_ + 1, 0);
-        for (int64_t e = 0; e < nE; ++e) {
-            pt_off[edges[e].point + 1]++;
-            if (slot[edges[e].pose] >= 0) ps_off[slot[edges[e].pose] + 1]++;
-        }
-        for (int q = 0; q < nX; ++q) pt_off[q + 1] += pt_off[q];
-        for (int s = 0; s < nF_; ++s) ps_off[s + 1] += ps_off[s];
-        std::vector<int32_t> pt_edges((size_t)std::max<int64_t>(nE, 1)), ps_edges((size_t)std::max<int64_t>(ps_off[nF_], 1));
-        std::vector<int32_t> table(points_fixed ? 1 : (size_t)std::max<int64_t>((int64_t)nF_ * nX, 1), -1);
-        {
-            std::vector<int64_t> f1(pt_off.begin(), pt_off.end() - 1), f2(ps_off.begin(), ps_off.end() - 1);
+        // slots of the free poses, the range check of every edge, the CSR by point and by free pose: ba_sparse_plan.hpp, shared with
+        // sivo_ba_analyze
+        std::vector<int32_t> slot, pt_edges, ps_edges;
+        std::vector<int64_t> pt_off, ps_off;
+        ba_index_edges(fixed, nP, nX, edges, nE, slot, nF_, pt_off, pt_edges, &ps_off, &ps_edges);
+        // the path of the reduced system: DENSE refuses nF nX > 2^28 here, in these words: "problem too large for the dense (free pose x
+        // point) edge table".  (Without landmarks in the state S is block diagonal: nothing to choose.)
+        sparse_ = ba_choose_path(solver, nF_, nX) == 2 && !points_fixed;
+        if (!sparse_) ba_choose_path(SIVO_BA_SOLVER_DENSE, nF_, nX);
+        // dense path: the (free pose, point) -> edge table
+        std::vector<int32_t> table(points_fixed || sparse_ ? 1 : (size_t)std::max<int64_t>((int64_t)nF_ * nX, 1), -1);
+        if (!points_fixed && !sparse_)
             for (int64_t e = 0; e < nE; ++e) {
-                pt_edges[f1[edges[e].point]++] = (int32_t)e;
                 const int s = slot[edges[e].pose];
-                if (s >= 0) {
-                    ps_edges[f2[s]++] = (int32_t)e;
-                    if (!points_fixed) {
-                        int32_t &t = table[(size_t)s * nX + edges[e].point];
-                        if (t >= 0) throw std::invalid_argument("two edges join the same (keyframe, map point) pair");
-                        t = (int32_t)e;
-                    }
-                }
+                if (s < 0) continue;
+                int32_t &t = table[(size_t)s * nX + edges[e].point];
+                if (t >= 0) throw std::invalid_argument("two edges join the same (keyframe, map point) pair");
+                t = (int32_t)e;
             }
-        }
+        // sparse path: the plan (pattern of S, order, symbolic factorisation, contribution lists), which also finds a doubled edge
+        BaSparsePlan sp;
+        if (sparse_) ba_sparse_plan(edges, slot.data(), nF_, nX, pt_off.data(), pt_edges.data(), sp);
         // ONE staged copy and ONE memset for the whole problem (round 6): the eleven uploads and thirteen memsets this constructor made until
         // round 5 were 24 blocking calls of ~15 us each — a tenth of the LocalBundleAdjustment call.  The host arrays are packed into the
         // calling thread's pinned staging buffer and go over in one asynchronous copy; everything that starts at zero is one region.
         {
             Layout L;
+            if (sparse_) {
+                const SparsePattern &pt = sp.pat;
+                const size_t nL = (size_t)pt.nL;
+                auto up = [&](const int32_t *&dst, const std::vector<int> &v) { L.copy(dst, v.data(), v.size() * 4); };
+                up(sd_.own_blk, sp.own_blk); up(sd_.con_ptr, sp.con_ptr); up(sd_.con, sp.con); up(sd_.perm, sp.perm);
+                up(sd_.lvl_ptr, pt.lvl_ptr); up(sd_.lvl_col, pt.lvl_col); up(sd_.off_ptr, pt.off_ptr); up(sd_.off_blk, pt.off_blk);
+                up(sd_.blk_col, pt.blk_col); up(sd_.pair_ptr, pt.pair_ptr); up(sd_.pairs, pt.pairs);
+                up(sd_.row_ptr, pt.row_ptr); up(sd_.row_lst, pt.row_lst); up(sd_.col_ptr, pt.col_ptr); up(sd_.col_lst, pt.col_lst);
+                L.zero(sd_.H, nL * 288);                          // (the fill blocks stay zero)
+                L.zero(sd_.b, (size_t)nF_ * 48); L.zero(sd_.L, nL * 288); L.zero(sd_.rinv, (size_t)nF_ * 48); L.zero(sd_.x, (size_t)nF_ * 48);
+                sd_.na = nF_; sd_.nlev = pt.nlev; sd_.n_own = (int)sp.own_blk.size();
+            }
             L.copy(slot_.p, slot.data(), slot.size() * 4); L.copy(pt_off_.p, pt_off.data(), pt_off.size() * 8);
             L.copy(pt_edges_.p, pt_edges.data(), pt_edges.size() * 4); L.copy(ps_off_.p, ps_off.data(), ps_off.size() * 8);
             L.copy(ps_edges_.p, ps_edges.data(), ps_edges.size() * 4); L.copy(table_.p, table.data(), table.size() * 4);
@@ -1372,7 +1529,7 @@ class BaSolver {
         SIVO_HIP(hipMemsetAsync(robust_.p, 1, (size_t)std::max<int64_t>(nE, 1), 0));
         for (int k = 0; k < 2; ++k) { Jp_[k].alloc((size_t)nE * 144); Jx_[k].alloc((size_t)nE * 72); wo_[k].alloc((size_t)nE * 8); W_[k].alloc((size_t)nE * 144); }
         Hll_.alloc((size_t)nX * 72); bl_.alloc((size_t)nX * 24); xl_.alloc((size_t)nX * 24);
-        S_.alloc((size_t)36 * nF_ * nF_ * 8);
+        if (!sparse_) S_.alloc((size_t)36 * nF_ * nF_ * 8);
         hpp_last_.assign((size_t)std::max(nF_, 1) * 36, 0.0);
         d_.edges = edges_.as<SivoEdge>(); d_.nE = nE; d_.slot = slot_.as<int32_t>();
         d_.level = level_.as<uint8_t>(); d_.robust = robust_.as<uint8_t>();
@@ -1420,7 +1577,7 @@ class BaSolver {
         slot_stage_->lm = lm;
         SIVO_HIP(hipMemcpyAsync(d_.lm, &slot_stage_->lm, sizeof lm, hipMemcpyHostToDevice, 0));
         if (!nF_) { slot_stage_->ok = 1.0; SIVO_HIP(hipMemcpyAsync(d_.scal + 3, &slot_stage_->ok, 8, hipMemcpyHostToDevice, 0)); }      // nothing to solve: "ok"
-        const bool lds_solve = 6 * nF_ <= 126 && dense_solve_lds_ok();
+        const bool lds_solve = !sparse_ && 6 * nF_ <= 126 && dense_solve_lds_ok();
         auto step = [&](bool first_of_call) {
             // linearise at the current estimate: errors, Jacobians, W (first step of a call only: afterwards the accepted trial left them);
             // Hll / bl of the points, Hpp / bp of the free poses, chi2 of the linearisation point (scal[6]) — skipped by the kernel itself
@@ -1429,7 +1586,10 @@ class BaSolver {
             hipLaunchKernelGGL(ba_build_kernel, dim3((landmarks ? gXb : 0u) + (unsigned)nF_ + 1u), dim3(BA_BUILD_T), 0, 0, d_, landmarks ? (int)gXb : 0);
             if (first_of_call) hipLaunchKernelGGL(ba_maxdiag_kernel, dim3(1), dim3(1024), 0, 0, d_, landmarks ? 1 : 0);
             // one trial
-            if (nF_) {
+            if (nF_ && sparse_) {
+                hipLaunchKernelGGL(ba_sparse_schur_kernel, dim3((unsigned)cdiv(sd_.n_own, BA_SP_T / 64)), dim3(BA_SP_T), 0, 0, d_, sd_);
+                hipLaunchKernelGGL(ba_sparse_solve_kernel, dim3(1), dim3(BA_SF_T), 0, 0, d_, sd_);
+            } else if (nF_) {
                 if (landmarks) {
                     hipLaunchKernelGGL(ba_schur_kernel, dim3((unsigned)(nF_ * (nF_ + 1) / 2)), dim3(BA_SCHUR_T), 0, 0, d_);
                 } else {
@@ -1491,11 +1651,13 @@ class BaSolver {
     }
     int free_slot(int pose) const { return pose >= 0 && pose < nP_ ? slot_host_[pose] : -1; }
     int n_free() const { return nF_; }
+    bool sparse() const { return sparse_; }
 
  private:
     int nP_, nX_, nF_ = 0;
     int64_t nE_;
-    bool points_fixed_;
+    bool points_fixed_, sparse_ = false;
+    BaSparseDev sd_{};
     int cur_ = 0;
     Buf slot_, pt_off_, pt_edges_, ps_off_, ps_edges_, table_, edges_, level_, robust_, poses_[2], points_[2];
     Buf err_[2], Jp_[2], Jx_[2], wo_[2], rchi_[2], W_[2], Hll_, bl_, xl_, sc_pt_, Hpp_, bp_, S_, xs_, scal_, partial_, counter_, lm_;
@@ -1511,17 +1673,18 @@ class BaSolver {
 
 using namespace sivo;
 
-extern "C" int sivo_ba_optimize(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
-                                const SivoEdge *edges, int64_t n_edges, const double intr[5], double delta_mono,
-                                double delta_stereo, const uint8_t *level, const uint8_t *robust, int iterations,
-                                const volatile uint8_t *stop_flag, double *err_out, double *hpp_last_out,
-                                int *iterations_run, int *trials) {
+extern "C" int sivo_ba_optimize_opts(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
+                                     const SivoEdge *edges, int64_t n_edges, const double intr[5], double delta_mono,
+                                     double delta_stereo, const uint8_t *level, const uint8_t *robust, int iterations,
+                                     const volatile uint8_t *stop_flag, double *err_out, double *hpp_last_out,
+                                     int *iterations_run, int *trials, const SivoBaOptions *opts) {
     return guarded([&] {
         if (!poses || !intr || (n_edges && !edges) || (n_points && !points)) throw std::invalid_argument("null argument");
         if (iterations < 0) throw std::invalid_argument("negative iteration count");
+        const int solver = ba_solver_option(opts);
         require_device();
         t_arena.reset();
-        BaSolver s(poses, pose_fixed, n_poses, points, n_points, false, edges, n_edges, intr, delta_mono, delta_stereo);
+        BaSolver s(poses, pose_fixed, n_poses, points, n_points, false, edges, n_edges, intr, delta_mono, delta_stereo, solver);
         s.set_flags(level, robust);
         int tr = 0;
         const int n = s.optimize(iterations, stop_flag, &tr);
@@ -1533,11 +1696,48 @@ extern "C" int sivo_ba_optimize(double *poses, const uint8_t *pose_fixed, int n_
     });
 }
 
+extern "C" int sivo_ba_optimize(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
+                                const SivoEdge *edges, int64_t n_edges, const double intr[5], double delta_mono,
+                                double delta_stereo, const uint8_t *level, const uint8_t *robust, int iterations,
+                                const volatile uint8_t *stop_flag, double *err_out, double *hpp_last_out,
+                                int *iterations_run, int *trials) {
+    return sivo_ba_optimize_opts(poses, pose_fixed, n_poses, points, n_points, edges, n_edges, intr, delta_mono, delta_stereo, level, robust,
+                                 iterations, stop_flag, err_out, hpp_last_out, iterations_run, trials, nullptr);
+}
+
+// What the sparse path plans for a problem, and the path the options take; no device.
+extern "C" int sivo_ba_analyze(const uint8_t *pose_fixed, int n_poses, int n_points, const SivoEdge *edges, int64_t n_edges,
+                               const SivoBaOptions *opts, int64_t out[8]) {
+    return guarded([&] {
+        if (!out || (n_edges && !edges)) throw std::invalid_argument("null argument");
+        const int solver = ba_solver_option(opts);
+        std::vector<int32_t> slot, pt_edges;
+        std::vector<int64_t> pt_off;
+        int nF = 0;
+        ba_index_edges(pose_fixed, n_poses, n_points, edges, n_edges, slot, nF, pt_off, pt_edges);
+        const int path = ba_choose_path(solver, nF, n_points);
+        BaSparsePlan sp;
+        ba_sparse_plan(edges, slot.data(), nF, n_points, pt_off.data(), pt_edges.data(), sp);
+        out[0] = nF; out[1] = sp.n_off; out[2] = sp.pat.nL - nF; out[3] = sp.nnzL; out[4] = sp.flops; out[5] = sp.pat.nlev;
+        out[6] = sp.n_pairs; out[7] = path;
+        return SIVO_OK;
+    });
+}
+
 extern "C" int sivo_local_ba(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
                              const SivoEdge *edges, int64_t n_edges, const double intr[5], const volatile uint8_t *stop_flag,
                              uint8_t *outlier, int cov_pose, double *cov, int *cov_ok, int *iterations, int *trials) {
+    return sivo_local_ba_opts(poses, pose_fixed, n_poses, points, n_points, edges, n_edges, intr, stop_flag, outlier, cov_pose, cov, cov_ok,
+                              iterations, trials, nullptr);
+}
+
+extern "C" int sivo_local_ba_opts(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
+                                  const SivoEdge *edges, int64_t n_edges, const double intr[5], const volatile uint8_t *stop_flag,
+                                  uint8_t *outlier, int cov_pose, double *cov, int *cov_ok, int *iterations, int *trials,
+                                  const SivoBaOptions *opts) {
     return guarded([&] {
         if (!poses || !intr || (n_edges && !edges) || (n_points && !points)) throw std::invalid_argument("null argument");
+        const int solver = ba_solver_option(opts);
         require_device();
         if (iterations) *iterations = 0;
         if (trials) *trials = 0;
@@ -1546,7 +1746,7 @@ extern "C" int sivo_local_ba(double *poses, const uint8_t *pose_fixed, int n_pos
         if (stop_flag && *stop_flag) return SIVO_OK;                         // :757-761
         t_arena.reset();
         BaSolver s(poses, pose_fixed, n_poses, points, n_points, false, edges, n_edges, intr,
-                   (double)std::sqrt(5.991f), (double)std::sqrt(7.815f));      // const float thHuber = sqrt(5.991f) (:646-647)
+                   (double)std::sqrt(5.991f), (double)std::sqrt(7.815f), solver);      // const float thHuber = sqrt(5.991f) (:646-647)
         int tr = 0;
         int n = s.optimize(5, stop_flag, &tr);                                // :763-764
         if (!(stop_flag && *stop_flag)) {                                     // bDoMore (:766-772)

@@ -33,6 +33,7 @@
 #include "sim3_common.hpp"
 #include "solver_common.hpp"
 #include "solver_host.hpp"
+#include "sparse_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -508,11 +509,10 @@ __global__ __launch_bounds__(EG_T) void eg_correct_points_kernel(const float *xy
 // ------------------------------------------------------------------------------------------------
 // host side: ordering and symbolic factorisation (once per call)
 // ------------------------------------------------------------------------------------------------
-struct EgPlan {
-    int n = 0, ne = 0, na = 0, nlev = 0, nL = 0, n_hoff = 0;
+struct EgPlan : SparsePattern {
+    int n = 0, ne = 0, n_hoff = 0;
     int64_t nnzL = 0, flops = 0;
-    std::vector<int> vpos, own_blk, own_ptr, own_con, lvl_ptr, lvl_col, off_ptr, off_blk, blk_col, pair_ptr, pairs, row_ptr, row_lst,
-        col_ptr, col_lst;
+    std::vector<int> vpos, own_blk, own_ptr, own_con;
 };
 
 static void eg_validate(const uint8_t *fixed, int n, const SivoSim3Edge *e, int ne) {
@@ -538,110 +538,20 @@ static void eg_plan(const uint8_t *fixed, int n, const SivoSim3Edge *e, int ne, 
     P.na = na;
     P.vpos.assign(n, -1);
     if (na == 0) return;
-    // minimum degree on the block graph with the explicit elimination graph; ties to the lower variable (= lower vertex index)
-    std::vector<std::vector<int>> adj(na);
+    // ordering (minimum degree, ties to the lower variable = lower vertex index), the blocks of L, the update lists and the levels:
+    // sparse_plan.hpp, on the pairs of variables an edge joins
+    std::vector<std::pair<int, int>> vp;
     for (int k = 0; k < ne; ++k) {
         const int a = vid[e[k].i], b = vid[e[k].j];
-        if (a >= 0 && b >= 0) { adj[a].push_back(b); adj[b].push_back(a); }
+        if (a >= 0 && b >= 0) vp.push_back({a, b});
     }
-    for (auto &l : adj) { std::sort(l.begin(), l.end()); l.erase(std::unique(l.begin(), l.end()), l.end()); }
-    std::vector<int> pos(na, -1), order;
-    std::vector<std::vector<int>> colv(na);   // per position: the variables of the column's pattern (eliminated later)
-    order.reserve(na);
-    std::vector<int> merged;
-    for (int step = 0; step < na; ++step) {
-        int best = -1;
-        size_t bd = 0;
-        for (int v = 0; v < na; ++v)
-            if (pos[v] < 0 && (best < 0 || adj[v].size() < bd)) { best = v; bd = adj[v].size(); }
-        pos[best] = step;
-        order.push_back(best);
-        colv[step] = adj[best];
-        for (int u : adj[best]) {             // the neighbours become a clique, best leaves the graph
-            merged.clear();
-            std::set_union(adj[u].begin(), adj[u].end(), adj[best].begin(), adj[best].end(), std::back_inserter(merged));
-            merged.erase(std::remove_if(merged.begin(), merged.end(), [&](int w) { return w == u || w == best; }), merged.end());
-            adj[u].swap(merged);
-        }
-        adj[best].clear();
-    }
-    for (int a = 0; a < na; ++a) P.vpos[var[a]] = pos[a];
-    // the blocks of L: diagonal p = position p, then the off-diagonal ones column by column, rows ascending
-    std::vector<std::vector<int>> colrows(na), colblk(na);
-    int nL = na;
-    for (int j = 0; j < na; ++j) {
-        for (int v : colv[j]) colrows[j].push_back(pos[v]);
-        std::sort(colrows[j].begin(), colrows[j].end());
-        for (size_t q = 0; q < colrows[j].size(); ++q) colblk[j].push_back(nL++);
-    }
-    P.nL = nL;
-    P.blk_col.assign(nL, 0);
-    std::vector<int> blk_row(nL, 0);
-    for (int j = 0; j < na; ++j) { P.blk_col[j] = j; blk_row[j] = j; }
-    for (int j = 0; j < na; ++j)
-        for (size_t q = 0; q < colrows[j].size(); ++q) { P.blk_col[colblk[j][q]] = j; blk_row[colblk[j][q]] = colrows[j][q]; }
-    // rows: per position i, the blocks (i, k < i) with k ascending
-    std::vector<std::vector<std::pair<int, int>>> rows(na);      // (k, block)
-    for (int j = 0; j < na; ++j)
-        for (size_t q = 0; q < colrows[j].size(); ++q) rows[colrows[j][q]].push_back({j, colblk[j][q]});
-    P.row_ptr.assign(na + 1, 0);
-    for (int i = 0; i < na; ++i) {
-        P.row_ptr[i + 1] = P.row_ptr[i] + (int)rows[i].size();
-        for (auto &kb : rows[i]) { P.row_lst.push_back(kb.second); P.row_lst.push_back(kb.first); }
-    }
-    P.col_ptr.assign(na + 1, 0);
-    for (int j = 0; j < na; ++j) {
-        P.col_ptr[j + 1] = P.col_ptr[j] + (int)colrows[j].size();
-        for (size_t q = 0; q < colrows[j].size(); ++q) { P.col_lst.push_back(colblk[j][q]); P.col_lst.push_back(colrows[j][q]); }
-    }
-    // the update lists: block (i, j) sums L_ik L_jk^T over k < j in both rows (k ascending); diagonal (j, j) over the whole row j
-    P.pair_ptr.assign(nL + 1, 0);
-    std::vector<std::vector<int>> blkpairs(nL);
-    for (int j = 0; j < na; ++j) {
-        for (auto &kb : rows[j]) { blkpairs[j].push_back(kb.second); blkpairs[j].push_back(kb.second); }
-        for (size_t q = 0; q < colrows[j].size(); ++q) {
-            const int i = colrows[j][q], blk = colblk[j][q];
-            const auto &ri = rows[i], &rj = rows[j];
-            size_t a = 0, b = 0;
-            while (a < ri.size() && b < rj.size()) {
-                if (ri[a].first < rj[b].first) ++a;
-                else if (ri[a].first > rj[b].first) ++b;
-                else { blkpairs[blk].push_back(ri[a].second); blkpairs[blk].push_back(rj[b].second); ++a; ++b; }
-            }
-        }
-    }
-    for (int b = 0; b < nL; ++b) {
-        P.pair_ptr[b + 1] = P.pair_ptr[b] + (int)blkpairs[b].size() / 2;
-        P.pairs.insert(P.pairs.end(), blkpairs[b].begin(), blkpairs[b].end());
-    }
-    // levels of the elimination tree (parent = first row of the column's pattern): a column sits one level above its highest child
-    std::vector<int> level(na, 0);
-    int nlev = 0;
-    for (int j = 0; j < na; ++j) {
-        nlev = std::max(nlev, level[j] + 1);
-        if (!colrows[j].empty()) { const int p = colrows[j][0]; level[p] = std::max(level[p], level[j] + 1); }
-    }
-    P.nlev = nlev;
-    P.lvl_ptr.assign(nlev + 1, 0);
-    P.off_ptr.assign(nlev + 1, 0);
-    std::vector<std::vector<int>> bylev(nlev);
-    for (int j = 0; j < na; ++j) bylev[level[j]].push_back(j);
-    for (int l = 0; l < nlev; ++l) {
-        for (int j : bylev[l]) {
-            P.lvl_col.push_back(j);
-            for (int blk : colblk[j]) P.off_blk.push_back(blk);
-        }
-        P.lvl_ptr[l + 1] = (int)P.lvl_col.size();
-        P.off_ptr[l + 1] = (int)P.off_blk.size();
-    }
+    sparse_pattern(na, vp, P);
+    const int nL = P.nL;
+    for (int a = 0; a < na; ++a) P.vpos[var[a]] = P.pos[a];
     // assembly owners: every diagonal block, and every off-diagonal block an edge between two variables touches; contributions in
     // edge order (vertex-0 side first for the diagonal blocks)
     std::vector<std::vector<int>> con(nL);
-    auto find_blk = [&](int i, int j) {      // the L block (i > j, j)
-        const auto &cr = colrows[j];
-        const size_t q = std::lower_bound(cr.begin(), cr.end(), i) - cr.begin();
-        return colblk[j][q];
-    };
+    auto find_blk = [&](int i, int j) { return P.find_blk(i, j); };
     std::vector<char> hoff(nL, 0);
     for (int k = 0; k < ne; ++k) {
         const int pi = P.vpos[e[k].i], pj = P.vpos[e[k].j];

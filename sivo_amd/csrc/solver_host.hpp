@@ -120,7 +120,7 @@ class Layout {
         r_[n_++] = Region{slot, s, src, bytes, end_[kind], kind};
         end_[kind] += (std::max<size_t>(bytes, 8) + 255) / 256 * 256;
     }
-    static constexpr int kMax = 32;
+    static constexpr int kMax = 64;
     Region r_[kMax];
     int n_ = 0;
     size_t end_[3] = {0, 0, 0};

@@ -6,7 +6,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Edge, Sim3Edge, Sim3Match, Sim3Problem, check, lib
+from ._lib import BaOptions, Edge, Sim3Edge, Sim3Match, Sim3Problem, check, lib
 
 EDGE_DTYPE = np.dtype([("pose", np.int32), ("point", np.int32), ("stereo", np.int32), ("pad_", np.int32),
                        ("obs", np.float64, 3), ("inv_sigma2", np.float64)])
@@ -56,32 +56,59 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+BA_SOLVERS = {"auto": 0, "dense": 1, "sparse": 2}      # SIVO_BA_SOLVER_*
+
+
+def _ba_options(solver):
+    """The SivoBaOptions of a solver name; None for "auto" (the plain entry points)."""
+    if solver not in BA_SOLVERS:
+        raise ValueError(f"solver must be one of {sorted(BA_SOLVERS)}, not {solver!r}")
+    return None if solver == "auto" else BaOptions(C.sizeof(BaOptions), BA_SOLVERS[solver])
+
+
 def ba_optimize(poses, fixed, points, edges, intr, iterations, level=None, robust=None,
-                delta_mono=float(np.sqrt(np.float32(5.991))), delta_stereo=float(np.sqrt(np.float32(7.815))), stop=None):
-    """One g2o optimize(iterations) call (Optimizer::BundleAdjustment, reference Optimizer.cc:49-271) on arrays."""
+                delta_mono=float(np.sqrt(np.float32(5.991))), delta_stereo=float(np.sqrt(np.float32(7.815))), stop=None, solver="auto"):
+    """One g2o optimize(iterations) call (Optimizer::BundleAdjustment, reference Optimizer.cc:49-271) on arrays.  solver: how the
+    reduced camera system is solved, "dense", "sparse" or "auto" (sparse from 64 free keyframes on, or when the dense edge table would
+    be refused)."""
     poses = np.array(poses, np.float64).reshape(-1, 12).copy(); points = np.array(points, np.float64).reshape(-1, 3).copy()
     fixed = np.ascontiguousarray(fixed, np.uint8); edges = np.ascontiguousarray(edges, EDGE_DTYPE)
     nE = edges.shape[0]
     level = None if level is None else np.ascontiguousarray(level, np.uint8)
     robust = None if robust is None else np.ascontiguousarray(robust, np.uint8)
     err = np.zeros((nE, 3)); hpp = np.zeros((int((fixed == 0).sum()), 6, 6)); n = C.c_int(0); tr = C.c_int(0)
-    check(lib().sivo_ba_optimize(_vp(poses), _vp(fixed), poses.shape[0], _vp(points), points.shape[0], _vp(edges), nE,
-                                 _intr(intr), delta_mono, delta_stereo, _vp(level), _vp(robust), iterations,
-                                 C.addressof(stop) if stop is not None else None, _vp(err), _vp(hpp), C.byref(n), C.byref(tr)))
+    args = (_vp(poses), _vp(fixed), poses.shape[0], _vp(points), points.shape[0], _vp(edges), nE, _intr(intr), delta_mono, delta_stereo,
+            _vp(level), _vp(robust), iterations, C.addressof(stop) if stop is not None else None, _vp(err), _vp(hpp), C.byref(n), C.byref(tr))
+    opts = _ba_options(solver)
+    check(lib().sivo_ba_optimize(*args) if opts is None else lib().sivo_ba_optimize_opts(*args, C.addressof(opts)))
     return {"poses": poses, "points": points, "err": err, "hpp": hpp, "iterations": n.value, "trials": tr.value}
 
 
-def local_ba(poses, fixed, points, edges, intr, cov_pose=-1, stop=None):
-    """Optimizer::LocalBundleAdjustment (reference Optimizer.cc:757-926) on arrays; `stop` is a ctypes c_uint8 (the reference's bool *pbStopFlag) or None."""
+def local_ba(poses, fixed, points, edges, intr, cov_pose=-1, stop=None, solver="auto"):
+    """Optimizer::LocalBundleAdjustment (reference Optimizer.cc:757-926) on arrays; `stop` is a ctypes c_uint8 (the reference's bool *pbStopFlag) or None;
+    solver as in ba_optimize."""
     poses = np.array(poses, np.float64).reshape(-1, 12).copy(); points = np.array(points, np.float64).reshape(-1, 3).copy()
     fixed = np.ascontiguousarray(fixed, np.uint8); edges = np.ascontiguousarray(edges, EDGE_DTYPE)
     nE = edges.shape[0]
     outlier = np.zeros(nE, np.uint8); cov = np.zeros((6, 6)); ok = C.c_int(0); n = C.c_int(0); tr = C.c_int(0)
-    check(lib().sivo_local_ba(_vp(poses), _vp(fixed), poses.shape[0], _vp(points), points.shape[0], _vp(edges), nE,
-                              _intr(intr), C.addressof(stop) if stop is not None else None, _vp(outlier), cov_pose,
-                              _vp(cov), C.byref(ok), C.byref(n), C.byref(tr)))
+    args = (_vp(poses), _vp(fixed), poses.shape[0], _vp(points), points.shape[0], _vp(edges), nE, _intr(intr),
+            C.addressof(stop) if stop is not None else None, _vp(outlier), cov_pose, _vp(cov), C.byref(ok), C.byref(n), C.byref(tr))
+    opts = _ba_options(solver)
+    check(lib().sivo_local_ba(*args) if opts is None else lib().sivo_local_ba_opts(*args, C.addressof(opts)))
     return {"poses": poses, "points": points, "outlier": outlier, "cov": cov, "cov_ok": bool(ok.value),
             "iterations": n.value, "trials": tr.value}
+
+
+def ba_analyze(fixed, n_points, edges, solver="auto"):
+    """What the sparse path of the bundle adjustment plans for a problem, host only: free poses, blocks of S below the diagonal,
+    off-diagonal blocks of L, nnz(L) (scalars, lower triangle), flops of one numeric factorisation, elimination-tree levels,
+    contribution pairs, and the path `solver` takes (1 dense, 2 sparse)."""
+    fixed = np.ascontiguousarray(fixed, np.uint8); edges = np.ascontiguousarray(edges, EDGE_DTYPE)
+    out = np.zeros(8, np.int64)
+    opts = _ba_options(solver)
+    check(lib().sivo_ba_analyze(_vp(fixed), fixed.shape[0], int(n_points), _vp(edges), edges.shape[0],
+                                None if opts is None else C.addressof(opts), _vp(out)))
+    return dict(zip(("free_poses", "s_blocks", "l_blocks", "nnz_l", "flops", "levels", "pairs", "path"), (int(v) for v in out)))
 
 
 def pose_optimize(pose0, points, edges, intr):
