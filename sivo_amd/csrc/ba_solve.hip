@@ -26,6 +26,12 @@
 // single persistent workgroup: the loop is latency-bound, so there is nothing to gain from more CUs
 // and everything to gain from not crossing the host 100+ times per frame.
 // The BA kernels are HBM-bound gathers/reductions; the LM accept/reject logic reads 3 doubles per trial.
+//
+// Host side (solver_host.hpp, as every other solver): a SolverCtx per calling thread and device — a non-blocking stream of its own (a
+// solve neither waits for nor holds up the null stream, which is also PyTorch's default), grow-only pinned and device buffers —, ONE
+// Layout per problem placed straight into BaDev / BaSparseDev and uploaded in one staged copy and one memset, results read back through
+// pinned memory behind one synchronisation per optimize() batch and one for everything a call returns; nothing is allocated in a call
+// once the buffers fit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -699,21 +705,6 @@ __global__ __launch_bounds__(BA_T) void ba_edge_kernel(BaDev d, double *partial 
         if (threadIdx.x == 0) d.scal[4] = sc4;
     }
     if (threadIdx.x == 0) { d.lm->last_set = buf; ba_lm_decide(d, chi, sc4, with_points); }
-}
-
-// out[0] = sum(in[0..n)) in a fixed order; one workgroup per sum (blockIdx.x = 1: the second sum, when given).  Four independent
-// partial sums per thread: the loop is a chain of dependent additions behind L2 loads otherwise (9.4 us for 36 k values).
-__global__ __launch_bounds__(1024) void ba_sum_kernel(const double *in, int64_t n, double *out, const double *in2 = nullptr, int64_t n2 = 0,
-                                                      double *out2 = nullptr) {
-    __shared__ double s_red[16], s_out[1];
-    if (blockIdx.x == 1) { in = in2; n = n2; out = out2; }
-    double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-    int64_t i = threadIdx.x;
-    for (; i + 3072 < n; i += 4096) { p0 += in[i]; p1 += in[i + 1024]; p2 += in[i + 2048]; p3 += in[i + 3072]; }
-    for (; i < n; i += 1024) p0 += in[i];
-    double v[1] = {(p0 + p1) + (p2 + p3)};
-    block_sum<1, 1024>(v, s_red, s_out);
-    if (threadIdx.x == 0) out[0] = s_out[0];
 }
 
 // Hll, bl of every point from its active edges (CSR order)
@@ -1401,41 +1392,6 @@ __global__ __launch_bounds__(BA_T) void ba_classify_kernel(BaDev d, const double
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// Per-thread, grow-only device arena: a solver call makes ~30 allocations; hipMalloc / hipFree each cost tens of
-// microseconds and hipFree synchronises the device, which is most of a 10 ms LocalBundleAdjustment.  Chunks are kept
-// between calls (PoseOptimization runs every frame on the tracking thread, LocalBundleAdjustment on the mapping
-// thread: one arena each) and released when the thread exits.
-struct BaArena {
-    struct Chunk { char *p; size_t cap, used; int device; };
-    std::vector<Chunk> chunks;
-    ~BaArena() { for (Chunk &c : chunks) (void)hipFree(c.p); }
-    void reset() { for (Chunk &c : chunks) c.used = 0; }
-    void *take(size_t bytes) {
-        bytes = (bytes + 255) / 256 * 256;
-        int dev = 0;
-        SIVO_HIP(hipGetDevice(&dev));
-        for (Chunk &c : chunks)
-            if (c.device == dev && c.cap - c.used >= bytes) { void *r = c.p + c.used; c.used += bytes; return r; }
-        Chunk c{nullptr, std::max(bytes, (size_t)64 << 20), 0, dev};
-        SIVO_HIP(hipMalloc((void **)&c.p, c.cap));
-        c.used = bytes;
-        chunks.push_back(c);
-        return c.p;
-    }
-};
-static thread_local BaArena t_arena;
-// Per-thread pinned staging buffer for a solver's one upload.  Its content is in flight until the call's first blocking read (the LM
-// state after the first batch of steps), which every call makes before it returns.
-static thread_local PinnedBuf t_stage(8 << 20);
-
-struct Buf {
-    void *p = nullptr;
-    void alloc(size_t bytes) { p = t_arena.take(bytes ? bytes : 8); }
-    void upload(const void *src, size_t bytes) { alloc(bytes); if (bytes) SIVO_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice)); }
-    void zero(size_t bytes) { alloc(bytes); SIVO_HIP(hipMemset(p, 0, bytes ? bytes : 8)); }
-    template <class T> T *as() const { return (T *)p; }
-};
-
 // The LDS-resident Cholesky needs up to 127 KB of dynamic LDS: the opt-in is per device and per process, so it is made once
 // per device and its result is kept; a device that refuses it uses the global-memory kernel.
 static bool dense_solve_lds_ok() {
@@ -1449,27 +1405,41 @@ static bool dense_solve_lds_ok() {
     return !refused[dev];
 }
 
-// What the stop flag of a solver call needs, once per calling thread (a pinned allocation costs 0.2 ms: not per call): a pinned word the
-// device reads where the host loop read *stop, and an event to wait on while the host polls the caller's flag.
-struct BaStopCtx {
+// The bundle adjustment's state on the calling thread's device (LocalBundleAdjustment on the mapping thread, the global one on its own):
+// the solvers' context — normal priority: it must not preempt tracking's PoseOptimization — and what a stop flag needs, made at the first
+// call that passes one (a pinned allocation costs 0.2 ms: not per call): a pinned word the device reads where the host loop read *stop,
+// and an event to wait on while the host polls the caller's flag.  Both go when the context is rebuilt on another device.
+struct BaCtx : SolverCtx {
     int *word = nullptr;
     hipEvent_t ev = nullptr;
-    ~BaStopCtx() {
-        if (word) (void)hipHostFree(word);
-        if (ev) (void)hipEventDestroy(ev);
-    }
-    void ensure() {
+    BaCtx() : SolverCtx(false, 8 << 20, 1 << 20, 4 << 20) {}
+    ~BaCtx() { drop_stop(); }
+    void bind() { if (SolverCtx::bind()) drop_stop(); }
+    void ensure_stop() {
         if (!word) { SIVO_HIP(hipHostMalloc((void **)&word, 64, hipHostMallocCoherent | hipHostMallocMapped)); *word = 0; }      // (fine-grained: the device must not cache it)
         if (!ev) SIVO_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
+
+ private:
+    void drop_stop() {
+        if (word) (void)hipHostFree(word);
+        if (ev) (void)hipEventDestroy(ev);
+        word = nullptr; ev = nullptr;
+    }
 };
-static thread_local BaStopCtx t_stop;
+static BaCtx &ba_ctx() {
+    static thread_local BaCtx c;
+    c.bind();
+    return c;
+}
 
 class BaSolver {
  public:
+    // level / robust: the edges' flags (null: every edge active / with its kernel)
     BaSolver(const double *poses, const uint8_t *fixed, int nP, const double *points, int nX, bool points_fixed,
-             const SivoEdge *edges, int64_t nE, const double intr[5], double dm, double ds, int solver = SIVO_BA_SOLVER_AUTO)
-        : nP_(nP), nX_(nX), nE_(nE), points_fixed_(points_fixed) {
+             const SivoEdge *edges, int64_t nE, const uint8_t *level, const uint8_t *robust, const double intr[5], double dm, double ds,
+             int solver = SIVO_BA_SOLVER_AUTO)
+        : ctx_(ba_ctx()), nP_(nP), nX_(nX), nE_(nE), points_fixed_(points_fixed) {
         // slots of the free poses, the range check of every edge, the CSR by point and by free pose: ba_sparse_plan.hpp, shared with
         // sivo_ba_analyze
         std::vector<int32_t> slot, pt_edges, ps_edges;
@@ -1492,69 +1462,53 @@ class BaSolver {
         // sparse path: the plan (pattern of S, order, symbolic factorisation, contribution lists), which also finds a doubled edge
         BaSparsePlan sp;
         if (sparse_) ba_sparse_plan(edges, slot.data(), nF_, nX, pt_off.data(), pt_edges.data(), sp);
-        // ONE staged copy and ONE memset for the whole problem (round 6): the eleven uploads and thirteen memsets this constructor made until
-        // round 5 were 24 blocking calls of ~15 us each — a tenth of the LocalBundleAdjustment call.  The host arrays are packed into the
-        // calling thread's pinned staging buffer and go over in one asynchronous copy; everything that starts at zero is one region.
-        {
-            Layout L;
-            if (sparse_) {
-                const SparsePattern &pt = sp.pat;
-                const size_t nL = (size_t)pt.nL;
-                auto up = [&](const int32_t *&dst, const std::vector<int> &v) { L.copy(dst, v.data(), v.size() * 4); };
-                up(sd_.own_blk, sp.own_blk); up(sd_.con_ptr, sp.con_ptr); up(sd_.con, sp.con); up(sd_.perm, sp.perm);
-                up(sd_.lvl_ptr, pt.lvl_ptr); up(sd_.lvl_col, pt.lvl_col); up(sd_.off_ptr, pt.off_ptr); up(sd_.off_blk, pt.off_blk);
-                up(sd_.blk_col, pt.blk_col); up(sd_.pair_ptr, pt.pair_ptr); up(sd_.pairs, pt.pairs);
-                up(sd_.row_ptr, pt.row_ptr); up(sd_.row_lst, pt.row_lst); up(sd_.col_ptr, pt.col_ptr); up(sd_.col_lst, pt.col_lst);
-                L.zero(sd_.H, nL * 288);                          // (the fill blocks stay zero)
-                L.zero(sd_.b, (size_t)nF_ * 48); L.zero(sd_.L, nL * 288); L.zero(sd_.rinv, (size_t)nF_ * 48); L.zero(sd_.x, (size_t)nF_ * 48);
-                sd_.na = nF_; sd_.nlev = pt.nlev; sd_.n_own = (int)sp.own_blk.size();
-            }
-            L.copy(slot_.p, slot.data(), slot.size() * 4); L.copy(pt_off_.p, pt_off.data(), pt_off.size() * 8);
-            L.copy(pt_edges_.p, pt_edges.data(), pt_edges.size() * 4); L.copy(ps_off_.p, ps_off.data(), ps_off.size() * 8);
-            L.copy(ps_edges_.p, ps_edges.data(), ps_edges.size() * 4); L.copy(table_.p, table.data(), table.size() * 4);
-            L.copy(edges_.p, edges, (size_t)nE * sizeof(SivoEdge));
-            for (int k = 0; k < 2; ++k) { L.copy(poses_[k].p, poses, (size_t)nP * 96); L.copy(points_[k].p, points, (size_t)nX * 24); }
-            L.zero(level_.p, (size_t)nE);
-            for (int k = 0; k < 2; ++k) { L.zero(err_[k].p, (size_t)nE * 24); L.zero(rchi_[k].p, (size_t)nE * 8); }
-            L.zero(sc_pt_.p, (size_t)nX * 8); L.zero(Hpp_.p, (size_t)nF_ * 288); L.zero(bp_.p, (size_t)nF_ * 48); L.zero(xs_.p, (size_t)nF_ * 48);
-            L.zero(scal_.p, 8 * 8); L.zero(partial_.p, (size_t)cdiv64(std::max<int64_t>(nE, 1), BA_T) * 8); L.zero(counter_.p, 8);
-            L.zero(lm_.p, sizeof(BaLm));
-            // optimize() uploads its initial state from the slot behind the staged problem, which is still in flight then
-            char *host = t_stage.reserve(L.staged() + sizeof(LmSlot));
-            slot_stage_ = (LmSlot *)(host + L.staged());
-            L.place((char *)t_arena.take(L.bytes()), host);
-            L.send(0);
+        // ONE layout for everything the problem has on the device, every region placed straight into its BaDev / BaSparseDev field: the
+        // host arrays are packed into the calling thread's pinned staging buffer and go over in one asynchronous copy, everything that
+        // starts at zero is one memset, what the device writes first lies behind them.  (Until round 5 this constructor made eleven
+        // blocking uploads and thirteen memsets of ~15 us each — a tenth of the LocalBundleAdjustment call.)
+        Layout L;
+        if (sparse_) {
+            const SparsePattern &pt = sp.pat;
+            const size_t nL = (size_t)pt.nL;
+            auto up = [&](const int32_t *&dst, const std::vector<int> &v) { L.copy(dst, v.data(), v.size() * 4); };
+            up(sd_.own_blk, sp.own_blk); up(sd_.con_ptr, sp.con_ptr); up(sd_.con, sp.con); up(sd_.perm, sp.perm);
+            up(sd_.lvl_ptr, pt.lvl_ptr); up(sd_.lvl_col, pt.lvl_col); up(sd_.off_ptr, pt.off_ptr); up(sd_.off_blk, pt.off_blk);
+            up(sd_.blk_col, pt.blk_col); up(sd_.pair_ptr, pt.pair_ptr); up(sd_.pairs, pt.pairs);
+            up(sd_.row_ptr, pt.row_ptr); up(sd_.row_lst, pt.row_lst); up(sd_.col_ptr, pt.col_ptr); up(sd_.col_lst, pt.col_lst);
+            L.zero(sd_.H, nL * 288);                          // (the fill blocks stay zero)
+            L.zero(sd_.b, (size_t)nF_ * 48); L.zero(sd_.L, nL * 288); L.zero(sd_.rinv, (size_t)nF_ * 48); L.zero(sd_.x, (size_t)nF_ * 48);
+            sd_.na = nF_; sd_.nlev = pt.nlev; sd_.n_own = (int)sp.own_blk.size();
         }
-        robust_.alloc((size_t)nE);
-        SIVO_HIP(hipMemsetAsync(robust_.p, 1, (size_t)std::max<int64_t>(nE, 1), 0));
-        for (int k = 0; k < 2; ++k) { Jp_[k].alloc((size_t)nE * 144); Jx_[k].alloc((size_t)nE * 72); wo_[k].alloc((size_t)nE * 8); W_[k].alloc((size_t)nE * 144); }
-        Hll_.alloc((size_t)nX * 72); bl_.alloc((size_t)nX * 24); xl_.alloc((size_t)nX * 24);
-        if (!sparse_) S_.alloc((size_t)36 * nF_ * nF_ * 8);
-        hpp_last_.assign((size_t)std::max(nF_, 1) * 36, 0.0);
-        d_.edges = edges_.as<SivoEdge>(); d_.nE = nE; d_.slot = slot_.as<int32_t>();
-        d_.level = level_.as<uint8_t>(); d_.robust = robust_.as<uint8_t>();
-        d_.nP = nP; d_.nF = nF_; d_.nX = nX;
+        const size_t E = (size_t)nE, X = (size_t)nX, F = (size_t)nF_;
+        L.copy(d_.slot, slot.data(), slot.size() * 4); L.copy(d_.pt_off, pt_off.data(), pt_off.size() * 8);
+        L.copy(d_.pt_edges, pt_edges.data(), pt_edges.size() * 4); L.copy(d_.ps_off, ps_off.data(), ps_off.size() * 8);
+        L.copy(d_.ps_edges, ps_edges.data(), ps_edges.size() * 4); L.copy(d_.table, table.data(), table.size() * 4);
+        L.copy(d_.edges, edges, E * sizeof(SivoEdge));
+        for (int k = 0; k < 2; ++k) { L.copy(d_.poses[k], poses, (size_t)nP * 96); L.copy(d_.points[k], points, X * 24); }
+        if (level) L.copy(d_.level, level, E);
+        else L.zero(d_.level, E);
+        L.copy(d_.robust, robust, E);                         // (no flags given: every edge has its kernel, written below)
+        for (int k = 0; k < 2; ++k) { L.zero(d_.sets[k].err, E * 24); L.zero(d_.sets[k].rchi, E * 8); }
+        L.zero(d_.sc_pt, X * 8); L.zero(d_.Hpp, F * 288); L.zero(d_.bp, F * 48); L.zero(d_.xs, F * 48);
+        L.zero(d_.scal, 8 * 8); L.zero(partial_, (size_t)cdiv64(std::max<int64_t>(nE, 1), BA_T) * 8); L.zero(counter_, 8);
+        L.zero(d_.lm, sizeof(BaLm));
+        for (int k = 0; k < 2; ++k) { L.take(d_.sets[k].Jp, E * 144); L.take(d_.sets[k].Jx, E * 72); L.take(d_.sets[k].wo, E * 8); L.take(d_.sets[k].W, E * 144); }
+        L.take(d_.Hll, X * 72); L.take(d_.bl, X * 24); L.take(d_.xl, X * 24);
+        if (!sparse_) L.take(d_.S, 36 * F * F * 8);
+        L.take(flags_, E);
+        // what comes back through pinned memory: the LM state of a batch in front, behind it what download() fetches
+        out_ = ctx_.out.reserve(kOutHead + (size_t)nP * 96 + X * 24 + E * 25 + F * 288);
+        // optimize() uploads its initial state from the slot behind the staged problem, which is still in flight then
+        char *host = ctx_.in.reserve(L.staged() + sizeof(LmSlot));
+        slot_stage_ = (LmSlot *)(host + L.staged());
+        L.place(ctx_.dev.reserve(L.bytes()), host);
+        if (!robust && nE) std::memset(L.host(d_.robust), 1, E);
+        L.send(ctx_.stream);
+        d_.nE = nE; d_.nP = nP; d_.nF = nF_; d_.nX = nX;
         d_.K = Intr{intr[0], intr[1], intr[2], intr[3], intr[4]}; d_.delta_mono = dm; d_.delta_stereo = ds;
-        d_.pt_off = pt_off_.as<int64_t>(); d_.pt_edges = pt_edges_.as<int32_t>();
-        d_.ps_off = ps_off_.as<int64_t>(); d_.ps_edges = ps_edges_.as<int32_t>(); d_.table = table_.as<int32_t>();
-        for (int k = 0; k < 2; ++k) {
-            d_.sets[k].err = err_[k].as<double>(); d_.sets[k].Jp = Jp_[k].as<double>(); d_.sets[k].Jx = Jx_[k].as<double>();
-            d_.sets[k].wo = wo_[k].as<double>(); d_.sets[k].rchi = rchi_[k].as<double>(); d_.sets[k].W = W_[k].as<double>();
-        }
-        d_.Hll = Hll_.as<double>(); d_.bl = bl_.as<double>(); d_.xl = xl_.as<double>();
-        d_.sc_pt = sc_pt_.as<double>(); d_.Hpp = Hpp_.as<double>(); d_.bp = bp_.as<double>();
-        d_.S = S_.as<double>(); d_.xs = xs_.as<double>(); d_.scal = scal_.as<double>();
-        d_.lm = lm_.as<BaLm>();
-        for (int k = 0; k < 2; ++k) { d_.poses[k] = poses_[k].as<double>(); d_.points[k] = points_[k].as<double>(); }
         d_.abort = nullptr;
-        slot_host_ = slot;
+        slot_host_ = std::move(slot);
     }
-
-    void set_flags(const uint8_t *level, const uint8_t *robust) {
-        if (level && nE_) SIVO_HIP(hipMemcpy(level_.p, level, (size_t)nE_, hipMemcpyHostToDevice));
-        if (robust && nE_) SIVO_HIP(hipMemcpy(robust_.p, robust, (size_t)nE_, hipMemcpyHostToDevice));
-    }
-    void get_level(uint8_t *level) const { if (nE_) SIVO_HIP(hipMemcpy(level, level_.p, (size_t)nE_, hipMemcpyDeviceToHost)); }
 
     // g2o::SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg.  The loop itself runs on the device (BaLm): the
     // host enqueues one step per remaining iteration, reads the state once, and enqueues more only when a trial was rejected.
@@ -1563,45 +1517,43 @@ class BaSolver {
         const unsigned gE = (unsigned)cdiv64(std::max<int64_t>(nE_, 1), BA_T), gX4 = (unsigned)cdiv(std::max(nX_, 1) * BA_PL, BA_T);
         const bool landmarks = !points_fixed_ && nX_ > 0;
         const unsigned gXb = (unsigned)cdiv(std::max(nX_, 1) * BA_PL, BA_BUILD_T);
+        const hipStream_t st = ctx_.stream;
         if (stop) {
-            t_stop.ensure();
-            abort_host_ = t_stop.word;
-            *abort_host_ = 0;
-            d_.abort = abort_host_;
-        } else {
-            d_.abort = nullptr;
+            ctx_.ensure_stop();
+            *ctx_.word = 0;
         }
+        d_.abort = stop ? ctx_.word : nullptr;
         BaLm lm{};
         lm.ni = 2; lm.cur = cur_; lm.need_lin = 1; lm.first = 1; lm.it_limit = iterations; lm.last_set = last_set_;
-        // (from pinned memory: the copies read it after this call has returned; the previous optimize() ended with a blocking read)
+        // (from pinned memory: the copies read it after this call has returned; the previous optimize() ended with a synchronisation)
         slot_stage_->lm = lm;
-        SIVO_HIP(hipMemcpyAsync(d_.lm, &slot_stage_->lm, sizeof lm, hipMemcpyHostToDevice, 0));
-        if (!nF_) { slot_stage_->ok = 1.0; SIVO_HIP(hipMemcpyAsync(d_.scal + 3, &slot_stage_->ok, 8, hipMemcpyHostToDevice, 0)); }      // nothing to solve: "ok"
+        SIVO_HIP(hipMemcpyAsync(d_.lm, &slot_stage_->lm, sizeof lm, hipMemcpyHostToDevice, st));
+        if (!nF_) { slot_stage_->ok = 1.0; SIVO_HIP(hipMemcpyAsync(d_.scal + 3, &slot_stage_->ok, 8, hipMemcpyHostToDevice, st)); }      // nothing to solve: "ok"
         const bool lds_solve = !sparse_ && 6 * nF_ <= 126 && dense_solve_lds_ok();
         auto step = [&](bool first_of_call) {
             // linearise at the current estimate: errors, Jacobians, W (first step of a call only: afterwards the accepted trial left them);
             // Hll / bl of the points, Hpp / bp of the free poses, chi2 of the linearisation point (scal[6]) — skipped by the kernel itself
             // while trials of the same iteration go on
-            if (first_of_call) hipLaunchKernelGGL(ba_edge_kernel<true>, dim3(gE), dim3(BA_T), 0, 0, d_, (double *)nullptr, (unsigned *)nullptr, 0);
-            hipLaunchKernelGGL(ba_build_kernel, dim3((landmarks ? gXb : 0u) + (unsigned)nF_ + 1u), dim3(BA_BUILD_T), 0, 0, d_, landmarks ? (int)gXb : 0);
-            if (first_of_call) hipLaunchKernelGGL(ba_maxdiag_kernel, dim3(1), dim3(1024), 0, 0, d_, landmarks ? 1 : 0);
+            if (first_of_call) hipLaunchKernelGGL(ba_edge_kernel<true>, dim3(gE), dim3(BA_T), 0, st, d_, (double *)nullptr, (unsigned *)nullptr, 0);
+            hipLaunchKernelGGL(ba_build_kernel, dim3((landmarks ? gXb : 0u) + (unsigned)nF_ + 1u), dim3(BA_BUILD_T), 0, st, d_, landmarks ? (int)gXb : 0);
+            if (first_of_call) hipLaunchKernelGGL(ba_maxdiag_kernel, dim3(1), dim3(1024), 0, st, d_, landmarks ? 1 : 0);
             // one trial
             if (nF_ && sparse_) {
-                hipLaunchKernelGGL(ba_sparse_schur_kernel, dim3((unsigned)cdiv(sd_.n_own, BA_SP_T / 64)), dim3(BA_SP_T), 0, 0, d_, sd_);
-                hipLaunchKernelGGL(ba_sparse_solve_kernel, dim3(1), dim3(BA_SF_T), 0, 0, d_, sd_);
+                hipLaunchKernelGGL(ba_sparse_schur_kernel, dim3((unsigned)cdiv(sd_.n_own, BA_SP_T / 64)), dim3(BA_SP_T), 0, st, d_, sd_);
+                hipLaunchKernelGGL(ba_sparse_solve_kernel, dim3(1), dim3(BA_SF_T), 0, st, d_, sd_);
             } else if (nF_) {
                 if (landmarks) {
-                    hipLaunchKernelGGL(ba_schur_kernel, dim3((unsigned)(nF_ * (nF_ + 1) / 2)), dim3(BA_SCHUR_T), 0, 0, d_);
+                    hipLaunchKernelGGL(ba_schur_kernel, dim3((unsigned)(nF_ * (nF_ + 1) / 2)), dim3(BA_SCHUR_T), 0, st, d_);
                 } else {
-                    hipLaunchKernelGGL(ba_pose_only_system_kernel, dim3(64), dim3(256), 0, 0, d_);
+                    hipLaunchKernelGGL(ba_pose_only_system_kernel, dim3(64), dim3(256), 0, st, d_);
                 }
-                if (lds_solve) hipLaunchKernelGGL(ba_dense_solve_lds_kernel, dim3(1), dim3(BA_SOLVE_T), (size_t)(6 * nF_ + 1) * (6 * nF_ + 1) * 8, 0, d_);
-                else hipLaunchKernelGGL(ba_dense_solve_kernel, dim3(1), dim3(BA_SOLVE_T), 0, 0, d_);
+                if (lds_solve) hipLaunchKernelGGL(ba_dense_solve_lds_kernel, dim3(1), dim3(BA_SOLVE_T), (size_t)(6 * nF_ + 1) * (6 * nF_ + 1) * 8, st, d_);
+                else hipLaunchKernelGGL(ba_dense_solve_kernel, dim3(1), dim3(BA_SOLVE_T), 0, st, d_);
             }
             // (without landmarks in the state the points never move: both point buffers hold the caller's values from the upload on)
-            hipLaunchKernelGGL(ba_update_kernel, dim3(1u + (landmarks ? gX4 : 0u)), dim3(BA_T), 0, 0, d_);
+            hipLaunchKernelGGL(ba_update_kernel, dim3(1u + (landmarks ? gX4 : 0u)), dim3(BA_T), 0, st, d_);
             // the trial's errors and chi2; its last workgroup forms the sums and takes the decision (ba_lm_decide)
-            hipLaunchKernelGGL(ba_edge_kernel<false>, dim3(gE), dim3(BA_T), 0, 0, d_, partial_.as<double>(), counter_.as<unsigned>(), landmarks ? 1 : 0);
+            hipLaunchKernelGGL(ba_edge_kernel<false>, dim3(gE), dim3(BA_T), 0, st, d_, partial_, counter_, landmarks ? 1 : 0);
         };
         bool first = true;
         int steps_total = 0;
@@ -1612,12 +1564,13 @@ class BaSolver {
             SIVO_HIP(hipGetLastError());
             if (stop) {
                 // the caller's flag is host memory the device cannot see: poll it while the batch runs and pass it on through the pinned word
-                hipEvent_t ev = t_stop.ev;
-                SIVO_HIP(hipEventRecord(ev, 0));
-                while (hipEventQuery(ev) == hipErrorNotReady)
-                    if (*stop) *abort_host_ = 1;
+                SIVO_HIP(hipEventRecord(ctx_.ev, st));
+                while (hipEventQuery(ctx_.ev) == hipErrorNotReady)
+                    if (*stop) *ctx_.word = 1;
             }
-            SIVO_HIP(hipMemcpy(&lm, d_.lm, sizeof lm, hipMemcpyDeviceToHost));
+            SIVO_HIP(hipMemcpyAsync(out_, d_.lm, sizeof lm, hipMemcpyDeviceToHost, st));
+            SIVO_HIP(hipStreamSynchronize(st));
+            std::memcpy(&lm, out_, sizeof lm);
             if (lm.done || steps_total > 10 * iterations + 1) break;
         }
         cur_ = lm.cur; last_set_ = lm.last_set;
@@ -1625,48 +1578,59 @@ class BaSolver {
         return lm.it;
     }
 
-    // chi2 / depth classification at the current estimates using the error vectors g2o would hold
-    void classify(uint8_t *outlier_host, bool to_level, bool drop_kernels) {
+    // chi2 / depth classification at the current estimates using the error vectors g2o would hold.  as_level: the flags become the
+    // edges' levels (the kernel does not read the flags it replaces) and every robust kernel is dropped (:774-817); otherwise they are
+    // what download() hands out as `outlier`
+    void classify(bool as_level) {
         if (!nE_) return;
-        Buf out;
-        if (to_level && !outlier_host) out.p = level_.p;          // (the kernel does not read the flags it replaces)
-        else out.alloc((size_t)nE_);
-        hipLaunchKernelGGL(ba_classify_kernel, dim3((unsigned)cdiv64(nE_, BA_T)), dim3(BA_T), 0, 0, d_,
-                           (const double *)poses_[cur_].p, (const double *)points_[cur_].p, out.as<uint8_t>());
+        hipLaunchKernelGGL(ba_classify_kernel, dim3((unsigned)cdiv64(nE_, BA_T)), dim3(BA_T), 0, ctx_.stream, d_,
+                           (const double *)d_.poses[cur_], (const double *)d_.points[cur_], as_level ? const_cast<uint8_t *>(d_.level) : flags_);
         SIVO_HIP(hipGetLastError());
-        if (to_level && out.p != level_.p) SIVO_HIP(hipMemcpyAsync(level_.p, out.p, (size_t)nE_, hipMemcpyDeviceToDevice, 0));
-        if (drop_kernels) SIVO_HIP(hipMemsetAsync(robust_.p, 0, (size_t)nE_, 0));
-        if (outlier_host) SIVO_HIP(hipMemcpy(outlier_host, out.p, (size_t)nE_, hipMemcpyDeviceToHost));
+        if (as_level) SIVO_HIP(hipMemsetAsync(const_cast<uint8_t *>(d_.robust), 0, (size_t)nE_, ctx_.stream));
     }
 
-    void download(double *poses, double *points, double *err) const {
-        if (poses && nP_) SIVO_HIP(hipMemcpy(poses, poses_[cur_].p, (size_t)nP_ * 96, hipMemcpyDeviceToHost));
-        if (points && nX_ && !points_fixed_) SIVO_HIP(hipMemcpy(points, points_[cur_].p, (size_t)nX_ * 24, hipMemcpyDeviceToHost));
-        if (err && nE_) SIVO_HIP(hipMemcpy(err, err_[last_set_].p, (size_t)nE_ * 24, hipMemcpyDeviceToHost));
-    }
-    // H_pp of the last linearisation (computeMarginals inverts its block, Optimizer.cc:482-487, 900-907); fetched when asked for
-    const std::vector<double> &hpp_last() {
-        if (nF_) SIVO_HIP(hipMemcpy(hpp_last_.data(), d_.Hpp, (size_t)nF_ * 288, hipMemcpyDeviceToHost));
-        return hpp_last_;
+    // What the caller asked for (null: not this), through pinned memory behind ONE synchronisation: the estimates, the errors of the last
+    // evaluation, the flags of the last classify(false), and H_pp of the last linearisation (computeMarginals inverts a block of it,
+    // Optimizer.cc:482-487, 900-907) — of every free pose, or of slot `hpp_slot` alone.
+    void download(double *poses, double *points, double *err, uint8_t *outlier, double *hpp, int hpp_slot = -1) {
+        const hipStream_t st = ctx_.stream;
+        char *at = out_ + kOutHead;
+        struct { void *dst; const char *src; size_t bytes; } part[5];
+        int n = 0;
+        auto fetch = [&](void *dst, const void *dev, size_t bytes) {
+            if (!dst || !bytes) return;
+            SIVO_HIP(hipMemcpyAsync(at, dev, bytes, hipMemcpyDeviceToHost, st));
+            part[n].dst = dst; part[n].src = at; part[n].bytes = bytes; ++n;
+            at += bytes;
+        };
+        fetch(poses, d_.poses[cur_], (size_t)nP_ * 96);
+        fetch(points_fixed_ ? nullptr : points, d_.points[cur_], (size_t)nX_ * 24);
+        fetch(err, d_.sets[last_set_].err, (size_t)nE_ * 24);
+        if (hpp_slot < 0) fetch(hpp, d_.Hpp, (size_t)nF_ * 288);
+        else fetch(hpp, d_.Hpp + 36 * hpp_slot, 288);
+        fetch(outlier, flags_, (size_t)nE_);                  // (bytes: last, the doubles in front stay aligned)
+        SIVO_HIP(hipStreamSynchronize(st));
+        for (int i = 0; i < n; ++i) std::memcpy(part[i].dst, part[i].src, part[i].bytes);
     }
     int free_slot(int pose) const { return pose >= 0 && pose < nP_ ? slot_host_[pose] : -1; }
     int n_free() const { return nF_; }
     bool sparse() const { return sparse_; }
 
  private:
+    BaCtx &ctx_;                           // (the calling thread's, bound to its current device)
     int nP_, nX_, nF_ = 0;
     int64_t nE_;
     bool points_fixed_, sparse_ = false;
     BaSparseDev sd_{};
-    int cur_ = 0;
-    Buf slot_, pt_off_, pt_edges_, ps_off_, ps_edges_, table_, edges_, level_, robust_, poses_[2], points_[2];
-    Buf err_[2], Jp_[2], Jx_[2], wo_[2], rchi_[2], W_[2], Hll_, bl_, xl_, sc_pt_, Hpp_, bp_, S_, xs_, scal_, partial_, counter_, lm_;
-    int last_set_ = 0;
-    int *abort_host_ = nullptr;            // (the calling thread's pinned word, BaStopCtx)
-    struct LmSlot { BaLm lm; double ok; } *slot_stage_ = nullptr;      // (in t_stage)
-    std::vector<double> hpp_last_;
-    std::vector<int32_t> slot_host_;
     BaDev d_{};
+    double *partial_ = nullptr;            // the trial edge kernel's per-workgroup sums and its arrival counter
+    unsigned *counter_ = nullptr;
+    uint8_t *flags_ = nullptr;             // classify(false)'s output
+    int cur_ = 0, last_set_ = 0;
+    static constexpr size_t kOutHead = 256;
+    char *out_ = nullptr;                  // (in ctx_.out: a BaLm, from kOutHead on download()'s parts)
+    struct LmSlot { BaLm lm; double ok; } *slot_stage_ = nullptr;      // (in ctx_.in, behind the staged problem)
+    std::vector<int32_t> slot_host_;
 };
 
 }  // namespace sivo
@@ -1683,13 +1647,10 @@ extern "C" int sivo_ba_optimize_opts(double *poses, const uint8_t *pose_fixed, i
         if (iterations < 0) throw std::invalid_argument("negative iteration count");
         const int solver = ba_solver_option(opts);
         require_device();
-        t_arena.reset();
-        BaSolver s(poses, pose_fixed, n_poses, points, n_points, false, edges, n_edges, intr, delta_mono, delta_stereo, solver);
-        s.set_flags(level, robust);
+        BaSolver s(poses, pose_fixed, n_poses, points, n_points, false, edges, n_edges, level, robust, intr, delta_mono, delta_stereo, solver);
         int tr = 0;
         const int n = s.optimize(iterations, stop_flag, &tr);
-        s.download(poses, points, err_out);
-        if (hpp_last_out && s.n_free()) std::memcpy(hpp_last_out, s.hpp_last().data(), (size_t)s.n_free() * 288);
+        s.download(poses, points, err_out, nullptr, hpp_last_out);
         if (iterations_run) *iterations_run = n;
         if (trials) *trials = tr;
         return SIVO_OK;
@@ -1744,19 +1705,20 @@ extern "C" int sivo_local_ba_opts(double *poses, const uint8_t *pose_fixed, int 
         if (cov_ok) *cov_ok = 0;
         if (outlier && n_edges) std::memset(outlier, 0, (size_t)n_edges);
         if (stop_flag && *stop_flag) return SIVO_OK;                         // :757-761
-        t_arena.reset();
-        BaSolver s(poses, pose_fixed, n_poses, points, n_points, false, edges, n_edges, intr,
+        BaSolver s(poses, pose_fixed, n_poses, points, n_points, false, edges, n_edges, nullptr, nullptr, intr,
                    (double)std::sqrt(5.991f), (double)std::sqrt(7.815f), solver);      // const float thHuber = sqrt(5.991f) (:646-647)
         int tr = 0;
         int n = s.optimize(5, stop_flag, &tr);                                // :763-764
         if (!(stop_flag && *stop_flag)) {                                     // bDoMore (:766-772)
-            s.classify(nullptr, true, true);                                  // :774-817
+            s.classify(true);                                                 // :774-817
             n += s.optimize(10, stop_flag, &tr);                              // :820-821
         }
-        s.classify(outlier, false, false);                                    // :824-858
-        s.download(poses, points, nullptr);
-        if (cov && s.free_slot(cov_pose) >= 0) {
-            const bool ok = inv6_spd(s.hpp_last().data() + 36 * s.free_slot(cov_pose), cov);
+        s.classify(false);                                                    // :824-858
+        const int cov_slot = cov ? s.free_slot(cov_pose) : -1;
+        double hpp[36];
+        s.download(poses, points, nullptr, outlier, cov_slot >= 0 ? hpp : nullptr, cov_slot);
+        if (cov_slot >= 0) {
+            const bool ok = inv6_spd(hpp, cov);
             if (cov_ok) *cov_ok = ok;
         }
         if (iterations) *iterations = n;
@@ -1813,11 +1775,9 @@ extern "C" int sivo_pose_optimize(const double pose0[12], const double *points, 
             a.in = in; a.out = h_out; a.outlier = h_flag;
         } else {
             // edges beyond the LDS copy are read in every pass: they, and their flags, live in device memory
-            t_arena.reset();
-            Buf dIn, dOut;
-            dIn.alloc(in_doubles * 8); dOut.alloc(out_doubles * 8 + (size_t)n_edges);
-            SIVO_HIP(hipMemcpyAsync(dIn.p, in, in_doubles * 8, hipMemcpyHostToDevice, c.stream));
-            a.in = dIn.as<double>(); a.out = dOut.as<double>(); a.outlier = (uint8_t *)(dOut.as<double>() + out_doubles);
+            double *d_in = (double *)c.dev.reserve((in_doubles + out_doubles) * 8 + (size_t)n_edges), *d_out = d_in + in_doubles;
+            SIVO_HIP(hipMemcpyAsync(d_in, in, in_doubles * 8, hipMemcpyHostToDevice, c.stream));
+            a.in = d_in; a.out = d_out; a.outlier = (uint8_t *)(d_out + out_doubles);
         }
         hipLaunchKernelGGL(pose_optimize_kernel, dim3(1), dim3(PO_THREADS), (size_t)PO_LDS_BYTES, c.stream, a);
         SIVO_HIP(hipGetLastError());

@@ -1,5 +1,6 @@
-// solver_host.hpp — the host runtime shared by the device solvers (ba_solve.hip, sim3.hip, essential_graph.hip) and the entropy gate
-// (select.hip): grow-only staging buffers, a stream per device, and the layout of a one-copy upload.
+// solver_host.hpp — the host runtime shared by every device solver (ba_solve.hip, sim3.hip, essential_graph.hip, the RANSACs, the
+// mapping and loop-closing entry points) and the entropy gate (select.hip): grow-only staging buffers, a stream per device, and the
+// layout of a one-copy upload.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,15 +53,16 @@ struct SolverCtx {
     SolverCtx(bool high_priority, size_t in_min, size_t out_min, size_t dev_min)
         : in(in_min), out(out_min), dev(dev_min), high_(high_priority) {}
     ~SolverCtx() { release(); }
-    void bind() {
+    bool bind() {                              // true: rebuilt (what an owner keeps beside it belongs to another device now)
         int d = 0;
         SIVO_HIP(hipGetDevice(&d));
-        if (d == device_) return;
+        if (d == device_) return false;
         release();
         int lo = 0, hi = 0;
         if (high_) SIVO_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
         SIVO_HIP(high_ ? hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi) : hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         device_ = d;
+        return true;
     }
 
  private:

@@ -158,3 +158,108 @@ def test_pose_optimization_edge_cases(oracle):
     bad = ek.copy(); bad["point"][0] = 10 ** 6
     with pytest.raises(ValueError):
         optimizer.pose_optimize(p0, pts, bad, intr)
+
+
+def _small_scene():
+    poses, pts, edges, intr = make_ba_scene(seed=4, n_kf=6, n_pts=300)
+    P0, fixed, X0 = _start(poses, pts, 2, 0)
+    return P0, fixed, X0, edges, intr
+
+
+def _in_new_thread(fn):
+    """fn() on a thread of its own: the solvers' buffers are per thread, so they start empty there."""
+    import threading
+    box = {}
+
+    def run():
+        try:
+            box["result"] = fn()
+        except BaseException as e:       # noqa: BLE001 (handed to the caller's thread)
+            box["error"] = e
+    t = threading.Thread(target=run); t.start(); t.join()
+    if "error" in box:
+        raise box["error"]
+    return box["result"]
+
+
+def _assert_same(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_solves_do_not_wait_for_the_default_stream():
+    """LocalBundleAdjustment (both paths), BundleAdjustment with a stop flag and PoseOptimization beyond the LDS copy run on streams of
+    their own and read their results through pinned memory: behind a kernel that occupies PyTorch's default (null) stream they return,
+    with the results of an undisturbed run, while that kernel is still running."""
+    import time
+    import torch
+    small = _small_scene()
+    rng = np.random.default_rng(2)
+    nE = len(small[3])
+    level = (rng.random(nE) < 0.2).astype(np.uint8); robust = (rng.random(nE) < 0.5).astype(np.uint8)
+    stop = C.c_uint8(0)                                                     # passed, never raised
+    poses, pts, edges, intr = make_ba_scene(seed=11, n_kf=2, n_pts=9000)
+    ek = edges[edges["pose"] == 1].copy()
+    assert len(ek) > 3000                                                   # more than pose_optimize_kernel keeps in LDS
+    p0 = perturb_pose(poses[1], np.random.default_rng(6))
+    calls = [lambda: optimizer.local_ba(*small, cov_pose=5, solver="dense"),
+             lambda: optimizer.local_ba(*small, cov_pose=5, solver="sparse"),
+             lambda: optimizer.ba_optimize(*small, 2, level, robust, stop=stop),
+             lambda: optimizer.pose_optimize(p0, pts, ek, intr)]
+    warm = [f() for f in calls]                  # buffers, the stop word and event, the kernel attributes now exist
+    t0 = time.perf_counter()
+    for f, w in zip(calls, warm):
+        _assert_same(f(), w)
+    t_warm = time.perf_counter() - t0
+    torch.cuda._sleep(1000)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    probe = 2_000_000
+    e0.record(); torch.cuda._sleep(probe); e1.record(); torch.cuda.synchronize()
+    per_cycle = e0.elapsed_time(e1) * 1e-3 / probe
+    want = min(max(0.3, 20 * t_warm), 2.0)
+    print(f"[default stream] warm calls {t_warm * 1e3:.2f} ms, spin {want:.2f} s ({per_cycle * 1e9:.2f} ns per cycle)")
+    busy = torch.cuda.Event()
+    torch.cuda._sleep(int(want / per_cycle)); busy.record()
+    try:
+        for f, w in zip(calls, warm):
+            r = f()
+            assert not busy.query()              # the call returned while the default stream was still busy
+            _assert_same(r, w)
+    finally:
+        torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("solver", ["dense", "sparse"])
+def test_ba_buffers_regrown_for_a_larger_problem_keep_no_state(solver):
+    """A small problem, config 5 (~36 k edges: the device and pinned buffers the small one left do not hold it), the small one again —
+    on a fresh thread, whose buffers start empty."""
+    small = _small_scene()
+    poses, pts, edges, intr = make_ba_scene()
+    big = (*_start(poses, pts, 2, 3), edges, intr)
+
+    def run():
+        return [optimizer.local_ba(*s, cov_pose=len(s[0]) - 1, solver=solver) for s in (small, big, small)]
+    first, mid, third = _in_new_thread(run)
+    assert first["iterations"] > 0 and mid["iterations"] > 0 and first["cov_ok"]
+    _assert_same(first, third)
+
+
+def test_ba_follows_the_calling_threads_device():
+    """The stream, the buffers, the stop word and its event belong to the device they were made on: all are rebuilt when the calling
+    thread's current device has changed."""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    small = _small_scene()
+    stop = C.c_uint8(0)
+    before = torch.cuda.current_device()
+    try:
+        res = []
+        for dev in (0, 1, 0):
+            torch.cuda.set_device(dev)
+            res.append(optimizer.local_ba(*small, cov_pose=5, stop=stop))
+    finally:
+        torch.cuda.set_device(before)
+    _assert_same(res[0], res[1])
+    _assert_same(res[0], res[2])
