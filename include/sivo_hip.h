@@ -1174,6 +1174,51 @@ int sivo_localmap_set_bad(sivo_localmap_t map, int n_points, const int32_t *poin
                           const int32_t *kf_idx, const uint8_t *kf_val);
 int sivo_localmap_destroy(sivo_localmap_t map);
 
+/* What changed in the map since the handle's tables were sent: whole rows, replaced or
+ * appended.  Existing indices keep their meaning and nothing is deleted (a removed
+ * object stays as a bad row until the next replace); the indices old n_points ..
+ * n_points - 1 and old n_kf .. n_kf - 1 are new and every one of them is listed. */
+typedef struct {
+    uint32_t size;                  /* sizeof(SivoLocalMapDelta) of the caller's header */
+    int32_t  n_kf, n_points;        /* the map's sizes AFTER the call; each >= the handle's */
+    /* points whose observation list or flag is replaced, appended points included */
+    int32_t  n_point_rows;
+    const int32_t *point_idx;       /* strictly increasing */
+    const int64_t *point_obs_off;   /* n_point_rows + 1, starts at 0 */
+    const int32_t *point_obs_kf;    /* in the order std::map<KeyFrame*, size_t> walks */
+    const uint8_t *point_bad;       /* n_point_rows */
+    /* keyframes whose rows are replaced, appended keyframes included: all rows of a listed keyframe */
+    int32_t  n_kf_rows;
+    const int32_t *kf_idx;          /* strictly increasing */
+    const uint8_t *kf_bad;          /* n_kf_rows */
+    const int32_t *kf_parent;       /* n_kf_rows, -1 none */
+    const int64_t *kf_slot_off;  const int32_t *kf_slot_point;   /* -1 null slot */
+    const int64_t *kf_covis_off; const int32_t *kf_covis_kf;
+    const int64_t *kf_child_off; const int32_t *kf_child_kf;
+    const int32_t *kf_order;        /* n_kf (new), a permutation; NULL = the handle's order with the
+                                       appended keyframes behind it in index order */
+} SivoLocalMapDelta;
+
+/* The delta's rows go to the device in one upload and the device builds the new tables
+ * from the old ones; one synchronisation.  Afterwards the handle behaves in
+ * every call exactly as one created from the full new tables.  A delta with nothing in
+ * it (no rows, the handle's sizes, kf_order NULL) does not touch the device.  Refused
+ * with SIVO_ERR_INVALID_ARGUMENT before any device is touched, the handle left as it
+ * was: a size that is not sizeof(SivoLocalMapDelta), n_kf or n_points below the
+ * handle's, point_idx / kf_idx not strictly increasing or out of range, a new index that
+ * is not listed, an offset array that does not start at 0 or decreases, a payload index
+ * outside the NEW ranges, a kf_order that is not a permutation of the new n_kf, a NULL
+ * array with a non-zero count.  An update on another thread sees the old map or the
+ * new one. */
+int sivo_localmap_apply(sivo_localmap_t map, const SivoLocalMapDelta *delta);
+/* out = n_kf, n_points, and the entries of obs_kf, slot_point, covis_kf, child_kf. */
+int sivo_localmap_sizes(sivo_localmap_t map, int64_t out[6]);
+/* The handle's tables into the caller's writable arrays, sized by sivo_localmap_sizes
+ * (an offset array has one entry more than its rows, and is not written where there
+ * are no rows); out->n_kf and out->n_points must be the handle's.  kf_order comes back
+ * as stored: the identity where the creator passed NULL. */
+int sivo_localmap_export(sivo_localmap_t map, SivoLocalMapTables *out);
+
 /* Tracking::UpdateLocalMap (Tracking.cc:1092-1093: UpdateLocalKeyFrames :1126-1235,
  * then UpdateLocalPoints :1096-1124) for one frame: one upload, the launches, one
  * download, one synchronisation.

@@ -237,6 +237,9 @@ SIGNATURES = {
     "sivo_localmap_replace": [_vp, _vp],
     "sivo_localmap_set_bad": [_vp, _i, _vp, _vp, _i, _vp, _vp],
     "sivo_localmap_destroy": [_vp],
+    "sivo_localmap_apply": [_vp, _vp],
+    "sivo_localmap_sizes": [_vp, _vp],
+    "sivo_localmap_export": [_vp, _vp],
     "sivo_localmap_update": [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp],
     "sivo_voc_create_from_text": [C.c_char_p, C.POINTER(_vp)],
     "sivo_voc_create": [_i, _i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_vp)],

@@ -2,6 +2,8 @@
 //     SIVO::LocalMapDevice<KeyFrame, MapPoint> dev;           owns a sivo_localmap_t and the pointer <-> index maps
 //     dev.Rebuild(vpAllKFs)                                   gathers the tables of include/sivo_hip.h once and uploads them
 //     dev.MarkBad(pKF) / dev.MarkBad(pMP)                     isBad() of one keyframe / point became true since the last Rebuild
+//     dev.Touch(pKF) / dev.Touch(pMP) / dev.TouchNeighbourhood(pKF)   the tables of an object changed (or the object is new) ...
+//     dev.Sync()                                              ... and ONE sivo_localmap_apply sends the rows of what was touched
 //     SIVO::UpdateLocalMap(dev, F, vpLocalKeyFrames, vpLocalMapPoints, pReferenceKF)
 //                                                             in place of UpdateLocalKeyFrames(); UpdateLocalPoints(); (:1092-1093)
 // as header-only templates.  UpdateLocalMap maps F.mvpMapPoints to indices, makes ONE call to sivo_localmap_update and writes back as the
@@ -15,7 +17,15 @@
 //
 // kf_order, the order in which the reference's std::map<KeyFrame *, int> walks (:1156), is std::less<KeyFrame *> over the pointers; the
 // children are listed as the std::set iterates.  A frame slot whose map point the handle does not know — one created after the last
-// Rebuild — is an error, never skipped: its votes would be missing.
+// Rebuild and never synced — is an error, never skipped: its votes would be missing.
+//
+// Between two Rebuilds the map is kept current by deltas.  Whoever changes an object records it: Touch(pKF) where a keyframe's slots,
+// covisibles, children, parent or flag changed, Touch(pMP) where a point's observations or flag changed, TouchNeighbourhood(pKF) for a
+// keyframe together with the points in its slots and its covisibles.  Sync() gathers the rows of the recorded objects only — an unknown
+// point in a touched keyframe's slots and an unknown keyframe met as an observer, covisible, child or parent are appended and gathered
+// as well — and makes one call.  Indices are stable: an object keeps its index until the next Rebuild, which also compacts.  Whatever
+// changed and was not touched is stale until it is touched or the map is rebuilt.  One mutex guards the pointer <-> index maps: Sync runs
+// on the local mapper's thread, UpdateLocalMap on the tracking thread.
 #ifndef SIVO_AMD_API_LOCALMAPADAPTER_H
 #define SIVO_AMD_API_LOCALMAPADAPTER_H
 
@@ -23,6 +33,7 @@
 #include <cstdint>
 #include <functional>
 #include <map>
+#include <mutex>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -53,6 +64,8 @@ class LocalMapDevice {
     // The tables of every keyframe of the map, in the vector's order (a keyframe's index is its position), and of every map point one of
     // them holds.  A covisible, child, parent or observer outside the vector is an error.
     void Rebuild(const std::vector<KeyFrameT *> &vpAllKFs) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        mTouchedKFs.clear(); mTouchedPoints.clear();
         mvpKFs = vpAllKFs;
         mKFIndex.clear(); mvpPoints.clear(); mPointIndex.clear();
         const size_t K = mvpKFs.size();
@@ -102,18 +115,141 @@ class LocalMapDevice {
     }
 
     void MarkBad(KeyFrameT *pKF) {
+        std::lock_guard<std::mutex> lock(mMutex);
         const int32_t k = Known(pKF, "keyframe to mark");
         const uint8_t one = 1;
         localmap_detail::check(sivo_localmap_set_bad(mHandle, 0, nullptr, nullptr, 1, &k, &one), "LocalMapDevice::MarkBad");
     }
     void MarkBad(MapPointT *pMP) {
+        std::lock_guard<std::mutex> lock(mMutex);
         const auto it = mPointIndex.find(pMP);
         if (it == mPointIndex.end()) throw std::invalid_argument("LocalMapDevice::MarkBad: the map point was created after the last Rebuild");
         const uint8_t one = 1;
         localmap_detail::check(sivo_localmap_set_bad(mHandle, 1, &it->second, &one, 0, nullptr, nullptr), "LocalMapDevice::MarkBad");
     }
 
-    // the index of a keyframe the last Rebuild listed
+    // An object whose tables changed since the last Rebuild or Sync, or a new one.
+    void Touch(KeyFrameT *pKF) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        if (pKF) mTouchedKFs.insert(pKF);
+    }
+    void Touch(MapPointT *pMP) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        if (pMP) mTouchedPoints.insert(pMP);
+    }
+    // The keyframe, the points in its slots and its covisibles: what ProcessNewKeyFrame, CreateNewMapPoints and SearchInNeighbors change.
+    void TouchNeighbourhood(KeyFrameT *pKF) {
+        if (!pKF) return;
+        const std::vector<MapPointT *> vpMPs = pKF->GetMapPointMatches();
+        const std::vector<KeyFrameT *> vNeighs = pKF->GetVectorCovisibleKeyFrames();
+        std::lock_guard<std::mutex> lock(mMutex);
+        mTouchedKFs.insert(pKF);
+        for (MapPointT *pMP : vpMPs)
+            if (pMP) mTouchedPoints.insert(pMP);
+        for (KeyFrameT *pN : vNeighs)
+            if (pN) mTouchedKFs.insert(pN);
+    }
+
+    // The rows of everything touched, and of everything new they lead to, in ONE sivo_localmap_apply; nothing touched: no call.
+    void Sync() {
+        std::lock_guard<std::mutex> lock(mMutex);
+        if (mTouchedKFs.empty() && mTouchedPoints.empty()) return;
+        if (!mHandle) throw std::invalid_argument("LocalMapDevice::Sync: Rebuild has not run");
+        const size_t K0 = mvpKFs.size(), P0 = mvpPoints.size();
+        struct KfRow { uint8_t bad; int32_t parent; std::vector<int32_t> slots, covis, children; };
+        std::map<int32_t, KfRow> kfRows;                               // by index: the delta lists its rows in increasing order
+        std::map<int32_t, std::pair<uint8_t, std::vector<int32_t>>> pointRows;
+        std::vector<KeyFrameT *> kfQueue(mTouchedKFs.begin(), mTouchedKFs.end());
+        std::vector<MapPointT *> pointQueue(mTouchedPoints.begin(), mTouchedPoints.end());
+        auto kfIndex = [&](KeyFrameT *pKF) {                           // an unknown keyframe is appended and gathered as well
+            auto it = mKFIndex.find(pKF);
+            if (it == mKFIndex.end()) {
+                it = mKFIndex.insert(std::make_pair(pKF, (int32_t)mvpKFs.size())).first;
+                mvpKFs.push_back(pKF);
+                kfQueue.push_back(pKF);
+            }
+            return it->second;
+        };
+        auto pointIndex = [&](MapPointT *pMP) {
+            auto it = mPointIndex.find(pMP);
+            if (it == mPointIndex.end()) {
+                it = mPointIndex.insert(std::make_pair(pMP, (int32_t)mvpPoints.size())).first;
+                mvpPoints.push_back(pMP);
+                pointQueue.push_back(pMP);
+            }
+            return it->second;
+        };
+        try {
+            while (!kfQueue.empty() || !pointQueue.empty()) {
+                if (!kfQueue.empty()) {
+                    KeyFrameT *pKF = kfQueue.back();
+                    kfQueue.pop_back();
+                    const int32_t k = kfIndex(pKF);
+                    if (kfRows.count(k)) continue;
+                    KfRow &row = kfRows[k];
+                    row.bad = pKF->isBad() ? 1 : 0;
+                    const std::vector<MapPointT *> vpMPs = pKF->GetMapPointMatches();
+                    for (MapPointT *pMP : vpMPs) row.slots.push_back(pMP ? pointIndex(pMP) : -1);
+                    const std::vector<KeyFrameT *> vNeighs = pKF->GetVectorCovisibleKeyFrames();
+                    for (size_t i = 0; i < vNeighs.size() && i < 10; ++i) row.covis.push_back(kfIndex(vNeighs[i]));      // (KeyFrame.cc:222-230)
+                    const std::set<KeyFrameT *> spChilds = pKF->GetChildren();
+                    for (KeyFrameT *pChild : spChilds) row.children.push_back(kfIndex(pChild));
+                    KeyFrameT *pParent = pKF->GetParent();
+                    row.parent = pParent ? kfIndex(pParent) : -1;
+                } else {
+                    MapPointT *pMP = pointQueue.back();
+                    pointQueue.pop_back();
+                    const int32_t p = pointIndex(pMP);
+                    if (pointRows.count(p)) continue;
+                    std::pair<uint8_t, std::vector<int32_t>> &row = pointRows[p];
+                    row.first = pMP->isBad() ? 1 : 0;
+                    const std::map<KeyFrameT *, size_t> observations = pMP->GetObservations();
+                    for (auto mit = observations.begin(); mit != observations.end(); mit++) row.second.push_back(kfIndex(mit->first));
+                }
+            }
+            // (a keyframe or point appended by the lambdas stands in its queue until its row is gathered: every new index is listed)
+            std::vector<int32_t> pointIdx, obsKf, kfIdx, parent, slotPoint, covisKf, childKf, order;
+            std::vector<int64_t> obsOff(1, 0), slotOff(1, 0), covisOff(1, 0), childOff(1, 0);
+            std::vector<uint8_t> pointBad, kfBad;
+            for (const auto &e : pointRows) {
+                pointIdx.push_back(e.first); pointBad.push_back(e.second.first);
+                obsKf.insert(obsKf.end(), e.second.second.begin(), e.second.second.end());
+                obsOff.push_back((int64_t)obsKf.size());
+            }
+            for (const auto &e : kfRows) {
+                kfIdx.push_back(e.first); kfBad.push_back(e.second.bad); parent.push_back(e.second.parent);
+                slotPoint.insert(slotPoint.end(), e.second.slots.begin(), e.second.slots.end());
+                slotOff.push_back((int64_t)slotPoint.size());
+                covisKf.insert(covisKf.end(), e.second.covis.begin(), e.second.covis.end());
+                covisOff.push_back((int64_t)covisKf.size());
+                childKf.insert(childKf.end(), e.second.children.begin(), e.second.children.end());
+                childOff.push_back((int64_t)childKf.size());
+            }
+            for (const auto &e : mKFIndex) order.push_back(e.second);  // the std::map walks in std::less<KeyFrame *>: kf_order
+            SivoLocalMapDelta d;
+            d.size = (uint32_t)sizeof(SivoLocalMapDelta);
+            d.n_kf = (int32_t)mvpKFs.size(); d.n_points = (int32_t)mvpPoints.size();
+            d.n_point_rows = (int32_t)pointIdx.size(); d.point_idx = pointIdx.data(); d.point_obs_off = obsOff.data(); d.point_obs_kf = obsKf.data();
+            d.point_bad = pointBad.data();
+            d.n_kf_rows = (int32_t)kfIdx.size(); d.kf_idx = kfIdx.data(); d.kf_bad = kfBad.data(); d.kf_parent = parent.data();
+            d.kf_slot_off = slotOff.data(); d.kf_slot_point = slotPoint.data(); d.kf_covis_off = covisOff.data(); d.kf_covis_kf = covisKf.data();
+            d.kf_child_off = childOff.data(); d.kf_child_kf = childKf.data(); d.kf_order = order.data();
+            localmap_detail::check(sivo_localmap_apply(mHandle, &d), "LocalMapDevice::Sync");
+            std::vector<int64_t> len(mvpKFs.size(), 0);                // mSlotOff follows, in O(keyframes)
+            for (size_t k = 0; k < K0; ++k) len[k] = mSlotOff[k + 1] - mSlotOff[k];
+            for (const auto &e : kfRows) len[(size_t)e.first] = (int64_t)e.second.slots.size();
+            mSlotOff.assign(mvpKFs.size() + 1, 0);
+            for (size_t k = 0; k < mvpKFs.size(); ++k) mSlotOff[k + 1] = mSlotOff[k] + len[k];
+        } catch (...) {                                                 // the handle is as it was: so are the maps, and the marks stay for a retry
+            for (size_t k = K0; k < mvpKFs.size(); ++k) mKFIndex.erase(mvpKFs[k]);
+            for (size_t p = P0; p < mvpPoints.size(); ++p) mPointIndex.erase(mvpPoints[p]);
+            mvpKFs.resize(K0); mvpPoints.resize(P0);
+            throw;
+        }
+        mTouchedKFs.clear(); mTouchedPoints.clear();
+    }
+
+    // the index of a keyframe the handle knows (the caller holds mMutex or is the only thread)
     int32_t Known(KeyFrameT *pKF, const char *role) const {
         const auto it = mKFIndex.find(pKF);
         if (it == mKFIndex.end()) throw std::invalid_argument(std::string("LocalMapDevice: a ") + role + " is not among the keyframes of the last Rebuild");
@@ -126,6 +262,9 @@ class LocalMapDevice {
     std::vector<MapPointT *> mvpPoints;
     std::map<MapPointT *, int32_t> mPointIndex;
     std::vector<int64_t> mSlotOff;          // the slot counts: they bound the point list of a call
+    std::mutex mMutex;                      // guards the maps above and the sets below
+    std::set<KeyFrameT *> mTouchedKFs;
+    std::set<MapPointT *> mTouchedPoints;
 };
 
 // In place of UpdateLocalKeyFrames(); UpdateLocalPoints(); (Tracking.cc:1092-1093).  Every keyframe and point of the handle is asked for
@@ -133,6 +272,7 @@ class LocalMapDevice {
 template <class KeyFrameT, class MapPointT, class FrameT>
 void UpdateLocalMap(LocalMapDevice<KeyFrameT, MapPointT> &dev, FrameT &F, std::vector<KeyFrameT *> &vpLocalKeyFrames,
                     std::vector<MapPointT *> &vpLocalMapPoints, KeyFrameT *&pReferenceKF) {
+    std::lock_guard<std::mutex> lock(dev.mMutex);                  // the whole call: it sees the map before a Sync or after it
     if (!dev.mHandle) throw std::invalid_argument("UpdateLocalMap: Rebuild has not run");
     const size_t S = (size_t)F.numSemanticKeys;
     std::vector<int32_t> framePoint(S, -1), kfMarked, pointMarked, prev;

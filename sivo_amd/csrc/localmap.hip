@@ -20,6 +20,18 @@
 // G and the list lengths stay on the device between the launches (hdr); the grids of the three point kernels are sized from a bound the
 // host knows: the handle's total slot count (the local list holds no keyframe twice), or the slot count of prev_local_kf where that is
 // larger.  first[] is part of the handle and is cleared by one memset at the head of every update, so no call sees an earlier one.
+//
+// sivo_localmap_apply keeps the handle current without sending the map again: a delta of replaced and appended rows goes up in one copy
+// and the new tables are built from the old ones in the handle's second buffer (ping-pong, both grow-only), whose pointers take the
+// place of the old ones under the handle's mutex once the call's one synchronisation has returned.  The per-item bodies and the check
+// are localmap_delta_math.hpp.  For obs, slots, covisibles and children alike (blockIdx.y is the table):
+// localmap_delta_mark_kernel    one thread per delta row: src[idx[j]] = j + 1 (src is zeroed, as long as the new row count).
+// localmap_delta_len_kernel     one thread per new row: its length, summed per block of 256.
+// localmap_delta_scan_kernel    the exclusive scan inside the block and the sum of the blocks before it, in one fixed order without
+//                               atomics, into the new int64 offsets; the last row writes the table's total.
+// localmap_delta_gather_kernel  one wave per new row copies it from the old pool or from the delta's, 64 entries at a time.
+// localmap_delta_flags_kernel   point_bad, kf_bad, parent and kf_order are device-to-device copies of the old arrays; the delta's rows
+//                               are scattered over them, and kf_order's tail is the appended indices where the caller gave no order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,6 +46,7 @@
 #include "solver_host.hpp"
 
 #include "localmap_math.hpp"
+#include "localmap_delta_math.hpp"
 
 namespace sivo {
 
@@ -322,6 +335,101 @@ __global__ __launch_bounds__(LP_THREADS) void localmap_set_bad_kernel(LmBadArgs 
     else if (i - a.n_points < a.n_kf) a.kf_bad[a.kf_idx[i - a.n_points]] = a.kf_val[i - a.n_points];
 }
 
+// ---- sivo_localmap_apply: the new tables from the old ones and a delta of rows (localmap_delta_math.hpp) -----------------------------
+struct LmdCall {
+    LmdCsr c[LMD_TABLES];
+    int32_t *block_sum[LMD_TABLES];        // one per block of LP_THREADS rows
+    int64_t *totals;                       // LMD_TABLES: the new entry counts
+    int32_t *src_p, *src_k;                // zeroed: n_points / n_kf (new)
+    int32_t n_point_rows, n_kf_rows, n_kf_old, n_kf_new, order_given;
+    const int32_t *point_idx, *kf_idx, *d_parent;
+    const uint8_t *d_point_bad, *d_kf_bad;
+    uint8_t *point_bad, *kf_bad;           // the new arrays: they hold a copy of the old ones when the flags kernel runs
+    int32_t *parent, *kf_order;
+};
+
+__global__ __launch_bounds__(LP_THREADS) void localmap_delta_mark_kernel(LmdCall a) {
+    const int i = blockIdx.x * LP_THREADS + (int)threadIdx.x;
+    if (i < a.n_point_rows) lmd_mark(a.src_p, a.point_idx, i);
+    else if (i - a.n_point_rows < a.n_kf_rows) lmd_mark(a.src_k, a.kf_idx, i - a.n_point_rows);
+}
+
+// pass 2a of the offsets: the rows of a block of LP_THREADS, summed.  blockIdx.y is the table.
+__global__ __launch_bounds__(LP_THREADS) void localmap_delta_len_kernel(LmdCall a) {
+    __shared__ int32_t wave_tot[LP_THREADS / 64];
+    const LmdCsr &c = a.c[blockIdx.y];
+    if ((int64_t)blockIdx.x * LP_THREADS >= c.n_new) return;            // the whole block
+    const int64_t r = (int64_t)blockIdx.x * LP_THREADS + threadIdx.x;
+    int32_t total;
+    (void)lm_block_excl_scan<LP_THREADS>(r < c.n_new ? lmd_row_len(c, (int32_t)r) : 0, wave_tot, total);
+    if (threadIdx.x == 0) a.block_sum[blockIdx.y][blockIdx.x] = total;
+}
+
+// x[0] + .. + x[n - 1], the same in every thread of the workgroup, summed in one fixed order: a strided partial sum per thread, a
+// butterfly over the wave, the waves in order
+__device__ inline int64_t lmd_block_base(const int32_t *x, int n, int64_t *wave_acc) {
+    long long s = 0;
+    for (int i = threadIdx.x; i < n; i += LP_THREADS) s += x[i];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if ((threadIdx.x & 63) == 0) wave_acc[threadIdx.x >> 6] = s;
+    __syncthreads();
+    int64_t r = 0;
+#pragma unroll
+    for (int w = 0; w < LP_THREADS / 64; ++w) r += wave_acc[w];
+    __syncthreads();
+    return r;
+}
+
+// pass 2b: the exclusive scan inside the block, the sum of the blocks before it; the last row writes the table's total
+__global__ __launch_bounds__(LP_THREADS) void localmap_delta_scan_kernel(LmdCall a) {
+    __shared__ int32_t wave_tot[LP_THREADS / 64];
+    __shared__ int64_t wave_acc[LP_THREADS / 64];
+    const int w = blockIdx.y, blk = blockIdx.x;
+    const LmdCsr &c = a.c[w];
+    if (c.n_new == 0) {
+        if (blk == 0 && threadIdx.x == 0) a.totals[w] = 0;
+        return;
+    }
+    if ((int64_t)blk * LP_THREADS >= c.n_new) return;                   // the whole block
+    const int64_t r = (int64_t)blk * LP_THREADS + threadIdx.x;
+    const int32_t len = r < c.n_new ? lmd_row_len(c, (int32_t)r) : 0;
+    int32_t total;
+    const int32_t excl = lm_block_excl_scan<LP_THREADS>(len, wave_tot, total);
+    const int64_t base = lmd_block_base(a.block_sum[w], blk, wave_acc);
+    if (r < c.n_new) c.new_off[r] = base + excl;
+    if (r == c.n_new - 1) {
+        c.new_off[c.n_new] = base + excl + len;
+        a.totals[w] = base + excl + len;
+    }
+}
+
+// one wave per new row: lane e takes the entries e, e + 64, ...
+__global__ __launch_bounds__(LP_THREADS) void localmap_delta_gather_kernel(LmdCall a) {
+    const LmdCsr &c = a.c[blockIdx.y];
+    const int64_t r = (int64_t)blockIdx.x * (LP_THREADS / 64) + (threadIdx.x >> 6);
+    if (r >= c.n_new) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t at = c.new_off[r];
+    const int32_t len = (int32_t)(c.new_off[r + 1] - at);
+    const int32_t *from = lmd_row_source(c, (int32_t)r);
+    for (int32_t e = lane; e < len; e += 64) c.new_val[at + e] = from[e];
+}
+
+// the delta's flags and parents over the copies of the old arrays; kf_order's tail where the caller gave no order
+__global__ __launch_bounds__(LP_THREADS) void localmap_delta_flags_kernel(LmdCall a) {
+    int i = blockIdx.x * LP_THREADS + (int)threadIdx.x;
+    if (i < a.n_point_rows) { a.point_bad[a.point_idx[i]] = a.d_point_bad[i] ? 1 : 0; return; }
+    i -= a.n_point_rows;
+    if (i < a.n_kf_rows) {
+        a.kf_bad[a.kf_idx[i]] = a.d_kf_bad[i] ? 1 : 0;
+        a.parent[a.kf_idx[i]] = a.d_parent[i];
+        return;
+    }
+    i -= a.n_kf_rows;
+    if (!a.order_given && i < a.n_kf_new - a.n_kf_old) a.kf_order[a.n_kf_old + i] = a.n_kf_old + i;
+}
+
 static void lm_throw(const char *what, const char *e) {
     if (e) throw std::invalid_argument(std::string(what) + ": " + e);
 }
@@ -339,7 +447,10 @@ using namespace sivo;
 struct sivo_localmap {
     std::mutex mu;
     int device = -1;
-    DeviceBuf dev{1 << 20};                // the tables and first[], grow-only
+    DeviceBuf buf_a{1 << 20}, buf_b{1 << 20};                  // the tables and first[] live in dev(cur), apply builds into the other; grow-only
+    DeviceBuf &dev(int i) { return i ? buf_b : buf_a; }
+    int cur = 0;
+    int64_t total[LMD_TABLES] = {0, 0, 0, 0};                  // the entries of obs_kf, slot_point, covis_kf, child_kf
     SivoLocalMapTables d{};                // device pointers
     uint32_t *first = nullptr;
     std::vector<int64_t> slot_off;         // host copy: the slot counts bound the grids and size prev_local_kf's walk
@@ -368,7 +479,7 @@ static void lm_load(sivo_localmap *m, const SivoLocalMapTables &t) {
     L.copy(d.kf_order, t.kf_order ? t.kf_order : identity.data(), 4 * K);
     L.take(first, 4 * P);
     std::vector<char> host(L.staged());
-    L.place(m->dev.reserve(L.bytes()), host.data());
+    L.place(m->dev(m->cur).reserve(L.bytes()), host.data());
     L.send(c.stream);
     SIVO_HIP(hipStreamSynchronize(c.stream));
     m->d = d;
@@ -376,6 +487,7 @@ static void lm_load(sivo_localmap *m, const SivoLocalMapTables &t) {
     m->slot_off.assign(K + 1, 0);
     if (K) std::memcpy(m->slot_off.data(), t.slot_off, 8 * (K + 1));
     m->total_slots = (int64_t)ns;
+    m->total[LMD_OBS] = (int64_t)no; m->total[LMD_SLOT] = (int64_t)ns; m->total[LMD_COVIS] = (int64_t)nc; m->total[LMD_CHILD] = (int64_t)nh;
 }
 
 extern "C" int sivo_localmap_create(const SivoLocalMapTables *t, sivo_localmap_t *map) {
@@ -413,7 +525,8 @@ extern "C" int sivo_localmap_destroy(sivo_localmap_t m) {
         if (!m) return SIVO_OK;
         {
             DeviceGuard dg(m->device);
-            m->dev.release();
+            m->dev(0).release();
+            m->dev(1).release();
         }
         delete m;
         return SIVO_OK;
@@ -507,6 +620,133 @@ extern "C" int sivo_localmap_update(sivo_localmap_t m, int n_slots, const int32_
         *n_local_points = np;
         if (np) std::memcpy(local_point, L.host(a.local_point), 4 * (size_t)np);
         if (counts && K) std::memcpy(counts, L.host(a.counts), 4 * K);
+        return SIVO_OK;
+    });
+}
+
+// The delta's rows in one upload, the four passes over each table, the flags and the order, the four totals back: one synchronisation.
+// The new tables are built in the handle's other buffer; the handle changes only after everything has succeeded.
+extern "C" int sivo_localmap_apply(sivo_localmap_t m, const SivoLocalMapDelta *dl) {
+    return guarded([&] {
+        if (!m) throw std::invalid_argument("sivo_localmap_apply: null handle");
+        std::lock_guard<std::mutex> lock(m->mu);
+        lm_throw("sivo_localmap_apply", lmd_check_delta(m->d.n_kf, m->d.n_points, m->total, dl, sizeof(SivoLocalMapDelta)));
+        if (lmd_is_empty(m->d.n_kf, m->d.n_points, *dl)) return SIVO_OK;
+        require_device();
+        DeviceGuard dg(m->device);
+        SolverCtx &c = lm_ctx();
+        const SivoLocalMapDelta &d = *dl;
+        const size_t K0 = (size_t)m->d.n_kf, P0 = (size_t)m->d.n_points, K1 = (size_t)d.n_kf, P1 = (size_t)d.n_points;
+        const size_t np = (size_t)d.n_point_rows, nk = (size_t)d.n_kf_rows;
+        const int32_t rows_old[LMD_TABLES] = {(int32_t)P0, (int32_t)K0, (int32_t)K0, (int32_t)K0};
+        const int32_t rows_new[LMD_TABLES] = {(int32_t)P1, (int32_t)K1, (int32_t)K1, (int32_t)K1};
+        const int64_t *old_off[LMD_TABLES] = {m->d.obs_off, m->d.slot_off, m->d.covis_off, m->d.child_off};
+        const int32_t *old_val[LMD_TABLES] = {m->d.obs_kf, m->d.slot_point, m->d.covis_kf, m->d.child_kf};
+        LmdCall a{};
+        const int32_t *d_order = nullptr;
+        unsigned nb[LMD_TABLES], nb_max = 1;
+        Layout L;                                                       // the call's staging: the delta, the marks, the block sums, the totals
+        L.copy(a.point_idx, d.point_idx, 4 * np); L.copy(a.d_point_bad, d.point_bad, np);
+        L.copy(a.kf_idx, d.kf_idx, 4 * nk); L.copy(a.d_kf_bad, d.kf_bad, nk); L.copy(a.d_parent, d.kf_parent, 4 * nk);
+        size_t bound[LMD_TABLES];                                       // old total + delta total: what the new pools are allocated from
+        for (int w = 0; w < LMD_TABLES; ++w) {
+            const int64_t *off;
+            const int32_t *val;
+            lmd_delta_table(d, w, off, val);
+            const size_t rows = w == LMD_OBS ? np : nk, entries = rows ? (size_t)off[rows] : 0;
+            L.copy(a.c[w].d_off, off, rows ? 8 * (rows + 1) : 0); L.copy(a.c[w].d_val, val, 4 * entries);
+            bound[w] = (size_t)m->total[w] + entries;
+            nb[w] = (unsigned)std::max(1, cdiv(rows_new[w], LP_THREADS));
+            nb_max = std::max(nb_max, nb[w]);
+        }
+        L.copy(d_order, d.kf_order, d.kf_order ? 4 * K1 : 0);
+        L.zero(a.src_p, 4 * P1); L.zero(a.src_k, 4 * K1);
+        for (int w = 0; w < LMD_TABLES; ++w) L.take(a.block_sum[w], 4 * (size_t)nb[w]);
+        L.take(a.totals, 8 * LMD_TABLES);
+        SivoLocalMapTables n{};                                         // the new tables, in the buffer the handle does not use
+        uint32_t *first = nullptr;
+        Layout N;
+        n.n_kf = d.n_kf; n.n_points = d.n_points;
+        N.take(n.obs_off, P1 ? 8 * (P1 + 1) : 0); N.take(n.obs_kf, 4 * bound[LMD_OBS]); N.take(n.point_bad, P1);
+        N.take(n.kf_bad, K1); N.take(n.slot_off, K1 ? 8 * (K1 + 1) : 0); N.take(n.slot_point, 4 * bound[LMD_SLOT]);
+        N.take(n.covis_off, K1 ? 8 * (K1 + 1) : 0); N.take(n.covis_kf, 4 * bound[LMD_COVIS]);
+        N.take(n.child_off, K1 ? 8 * (K1 + 1) : 0); N.take(n.child_kf, 4 * bound[LMD_CHILD]); N.take(n.parent, 4 * K1);
+        N.take(n.kf_order, 4 * K1); N.take(first, 4 * P1);
+        L.place(c.dev.reserve(L.bytes()), c.in.reserve(L.bytes()));
+        N.place(m->dev(1 - m->cur).reserve(N.bytes()), nullptr);
+        int64_t *new_off[LMD_TABLES] = {const_cast<int64_t *>(n.obs_off), const_cast<int64_t *>(n.slot_off), const_cast<int64_t *>(n.covis_off),
+                                        const_cast<int64_t *>(n.child_off)};
+        int32_t *new_val[LMD_TABLES] = {const_cast<int32_t *>(n.obs_kf), const_cast<int32_t *>(n.slot_point), const_cast<int32_t *>(n.covis_kf),
+                                        const_cast<int32_t *>(n.child_kf)};
+        for (int w = 0; w < LMD_TABLES; ++w) {
+            a.c[w].n_old = rows_old[w]; a.c[w].n_new = rows_new[w]; a.c[w].old_off = old_off[w]; a.c[w].old_val = old_val[w];
+            a.c[w].src = w == LMD_OBS ? a.src_p : a.src_k; a.c[w].new_off = new_off[w]; a.c[w].new_val = new_val[w];
+        }
+        a.n_point_rows = (int32_t)np; a.n_kf_rows = (int32_t)nk; a.n_kf_old = (int32_t)K0; a.n_kf_new = (int32_t)K1; a.order_given = d.kf_order ? 1 : 0;
+        a.point_bad = const_cast<uint8_t *>(n.point_bad); a.kf_bad = const_cast<uint8_t *>(n.kf_bad);
+        a.parent = const_cast<int32_t *>(n.parent); a.kf_order = const_cast<int32_t *>(n.kf_order);
+        L.send(c.stream);
+        if (P0) SIVO_HIP(hipMemcpyAsync(a.point_bad, m->d.point_bad, P0, hipMemcpyDeviceToDevice, c.stream));
+        if (K0) {
+            SIVO_HIP(hipMemcpyAsync(a.kf_bad, m->d.kf_bad, K0, hipMemcpyDeviceToDevice, c.stream));
+            SIVO_HIP(hipMemcpyAsync(a.parent, m->d.parent, 4 * K0, hipMemcpyDeviceToDevice, c.stream));
+        }
+        if (d.kf_order) SIVO_HIP(hipMemcpyAsync(a.kf_order, d_order, 4 * K1, hipMemcpyDeviceToDevice, c.stream));
+        else if (K0) SIVO_HIP(hipMemcpyAsync(a.kf_order, m->d.kf_order, 4 * K0, hipMemcpyDeviceToDevice, c.stream));
+        const unsigned rows_max = (unsigned)std::max<size_t>(1, std::max(P1, K1));
+        if (np + nk) hipLaunchKernelGGL(localmap_delta_mark_kernel, dim3((unsigned)cdiv64((int64_t)(np + nk), LP_THREADS)), dim3(LP_THREADS), 0, c.stream, a);
+        hipLaunchKernelGGL(localmap_delta_len_kernel, dim3(nb_max, LMD_TABLES), dim3(LP_THREADS), 0, c.stream, a);
+        hipLaunchKernelGGL(localmap_delta_scan_kernel, dim3(nb_max, LMD_TABLES), dim3(LP_THREADS), 0, c.stream, a);
+        hipLaunchKernelGGL(localmap_delta_gather_kernel, dim3((unsigned)cdiv64(rows_max, LP_THREADS / 64), LMD_TABLES), dim3(LP_THREADS), 0, c.stream, a);
+        const size_t n_flags = np + nk + (d.kf_order ? 0 : K1 - K0);
+        if (n_flags) hipLaunchKernelGGL(localmap_delta_flags_kernel, dim3((unsigned)cdiv64((int64_t)n_flags, LP_THREADS)), dim3(LP_THREADS), 0, c.stream, a);
+        SIVO_HIP(hipGetLastError());
+        SIVO_HIP(hipMemcpyAsync(L.host(a.totals), a.totals, 8 * LMD_TABLES, hipMemcpyDeviceToHost, c.stream));
+        SIVO_HIP(hipStreamSynchronize(c.stream));
+        const int64_t *totals = L.host(a.totals);
+        std::vector<int64_t> slot_off = lmd_host_slot_off(m->slot_off, (int32_t)K0, d);      // O(keyframes), on the host
+        if (totals[LMD_SLOT] != slot_off.back()) throw std::logic_error("sivo_localmap_apply: the device's slot total differs from the host's");
+        for (int w = 0; w < LMD_TABLES; ++w) m->total[w] = totals[w];   // the exact totals, not the bounds the pools were sized from
+        m->d = n;
+        m->first = first;
+        m->slot_off.swap(slot_off);
+        m->total_slots = m->total[LMD_SLOT];
+        m->cur = 1 - m->cur;
+        return SIVO_OK;
+    });
+}
+
+extern "C" int sivo_localmap_sizes(sivo_localmap_t m, int64_t out[6]) {
+    return guarded([&] {
+        if (!m) throw std::invalid_argument("sivo_localmap_sizes: null handle");
+        if (!out) throw std::invalid_argument("sivo_localmap_sizes: null out");
+        std::lock_guard<std::mutex> lock(m->mu);
+        out[0] = m->d.n_kf; out[1] = m->d.n_points;
+        for (int w = 0; w < LMD_TABLES; ++w) out[2 + w] = m->total[w];
+        return SIVO_OK;
+    });
+}
+
+extern "C" int sivo_localmap_export(sivo_localmap_t m, SivoLocalMapTables *out) {
+    return guarded([&] {
+        if (!m) throw std::invalid_argument("sivo_localmap_export: null handle");
+        std::lock_guard<std::mutex> lock(m->mu);
+        lm_throw("sivo_localmap_export", lmd_check_export(m->d.n_kf, m->d.n_points, m->total, out));
+        const size_t K = (size_t)m->d.n_kf, P = (size_t)m->d.n_points;
+        if (K == 0 && P == 0) return SIVO_OK;
+        require_device();
+        DeviceGuard dg(m->device);
+        SolverCtx &c = lm_ctx();
+        auto down = [&](const void *dst, const void *src, size_t bytes) {
+            if (bytes) SIVO_HIP(hipMemcpyAsync(const_cast<void *>(dst), src, bytes, hipMemcpyDeviceToHost, c.stream));
+        };
+        down(out->obs_off, m->d.obs_off, P ? 8 * (P + 1) : 0); down(out->obs_kf, m->d.obs_kf, 4 * (size_t)m->total[LMD_OBS]);
+        down(out->point_bad, m->d.point_bad, P); down(out->kf_bad, m->d.kf_bad, K);
+        down(out->slot_off, m->d.slot_off, K ? 8 * (K + 1) : 0); down(out->slot_point, m->d.slot_point, 4 * (size_t)m->total[LMD_SLOT]);
+        down(out->covis_off, m->d.covis_off, K ? 8 * (K + 1) : 0); down(out->covis_kf, m->d.covis_kf, 4 * (size_t)m->total[LMD_COVIS]);
+        down(out->child_off, m->d.child_off, K ? 8 * (K + 1) : 0); down(out->child_kf, m->d.child_kf, 4 * (size_t)m->total[LMD_CHILD]);
+        down(out->parent, m->d.parent, 4 * K); down(out->kf_order, m->d.kf_order, 4 * K);
+        SIVO_HIP(hipStreamSynchronize(c.stream));
         return SIVO_OK;
     });
 }

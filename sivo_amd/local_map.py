@@ -18,6 +18,18 @@ class _Tables(C.Structure):  # == SivoLocalMapTables
     _fields_ = [("n_kf", C.c_int32), ("n_points", C.c_int32)] + [(f, C.c_void_p) for f in TABLE_FIELDS]
 
 
+POINT_ROW_FIELDS = ("idx", "obs_off", "obs_kf", "bad")
+KF_ROW_FIELDS = ("idx", "bad", "parent", "slot_off", "slot_point", "covis_off", "covis_kf", "child_off", "child_kf")
+_ROW_DTYPE = dict(_DTYPE, idx=np.int32, bad=np.uint8)
+
+
+class _Delta(C.Structure):  # == SivoLocalMapDelta
+    _fields_ = ([("size", C.c_uint32), ("n_kf", C.c_int32), ("n_points", C.c_int32), ("n_point_rows", C.c_int32)]
+                + [(f, C.c_void_p) for f in ("point_idx", "point_obs_off", "point_obs_kf", "point_bad")] + [("n_kf_rows", C.c_int32)]
+                + [(f, C.c_void_p) for f in ("kf_idx", "kf_bad", "kf_parent", "kf_slot_off", "kf_slot_point", "kf_covis_off", "kf_covis_kf",
+                                             "kf_child_off", "kf_child_kf", "kf_order")])
+
+
 def _a(x, dt):
     return np.ascontiguousarray(x, dt).ravel()
 
@@ -39,7 +51,8 @@ class LocalMap:
     """The map as arrays over dense keyframe and point indices (SivoLocalMapTables of include/sivo_hip.h): obs_off / obs_kf (CSR point ->
     observing keyframes), point_bad, kf_bad, slot_off / slot_point (CSR keyframe -> GetMapPointMatches(), -1 for null), covis_off /
     covis_kf (mvpOrderedConnectedKeyFrames), child_off / child_kf (mspChildren in the set's order), parent (-1: none) and kf_order (the
-    keyframes in pointer order; None: 0, 1, 2 ...).  The arrays are uploaded here and stay on the device until replace() or close()."""
+    keyframes in pointer order; None: 0, 1, 2 ...).  The arrays are uploaded here and stay on the device until replace() or close();
+    apply() changes and appends rows on the device, sizes() and export() read the handle back."""
 
     def __init__(self, n_kf, **tables):
         self._h = C.c_void_p()
@@ -62,6 +75,60 @@ class LocalMap:
         """A new set of tables into the same handle."""
         st = self._struct(n_kf, tables)
         check(lib().sivo_localmap_replace(self._h, C.byref(st)))
+
+    def apply(self, n_kf, n_points, point_rows=None, kf_rows=None, kf_order=None):
+        """The rows that changed since the tables were sent, applied on the device (SivoLocalMapDelta).  n_kf, n_points: the map's sizes
+        after the call.  point_rows: dict(idx, obs_off, obs_kf, bad) — the points whose observation list or flag is replaced, appended
+        points included; kf_rows: dict(idx, bad, parent, slot_off, slot_point, covis_off, covis_kf, child_off, child_kf) — all rows of
+        every listed keyframe, appended keyframes included.  idx is strictly increasing and lists every new index.  kf_order: the new
+        order, or None for the handle's with the appended keyframes behind it.  A missing array is passed as NULL."""
+        pr, kr = dict(point_rows or {}), dict(kf_rows or {})
+        unknown = (set(pr) - set(POINT_ROW_FIELDS)) | (set(kr) - set(KF_ROW_FIELDS))
+        if unknown:
+            raise TypeError("unknown row array " + ", ".join(sorted(unknown)))
+        pr = {f: None if pr.get(f) is None else _a(pr[f], _ROW_DTYPE[f]) for f in POINT_ROW_FIELDS}
+        kr = {f: None if kr.get(f) is None else _a(kr[f], _ROW_DTYPE[f]) for f in KF_ROW_FIELDS}
+        order = None if kf_order is None else _a(kf_order, np.int32)
+        if order is not None and len(order) != int(n_kf):
+            raise ValueError("kf_order must hold n_kf entries")
+        n_pr = 0 if pr["idx"] is None else len(pr["idx"])
+        n_kr = 0 if kr["idx"] is None else len(kr["idx"])
+        for rows, n, fields in ((pr, n_pr, ("bad",)), (kr, n_kr, ("bad", "parent"))):
+            for f in fields + tuple(k for k in rows if k.endswith("_off")):
+                if rows[f] is not None and len(rows[f]) != n + f.endswith("_off"):
+                    raise ValueError("%s must hold one entry per row%s" % (f, " and one more" if f.endswith("_off") else ""))
+        for rows in (pr, kr):
+            for f in rows:
+                inner = f[:-4] + ("_point" if f == "slot_off" else "_kf")
+                if f.endswith("_off") and rows[f] is not None and len(rows[f]) and rows[inner] is not None and len(rows[inner]) < int(rows[f][-1]):
+                    raise ValueError("%s is shorter than %s says" % (inner, f))
+        st = _Delta(C.sizeof(_Delta), int(n_kf), int(n_points), n_pr, _p(pr["idx"]), _p(pr["obs_off"]), _p(pr["obs_kf"]), _p(pr["bad"]), n_kr,
+                    _p(kr["idx"]), _p(kr["bad"]), _p(kr["parent"]), _p(kr["slot_off"]), _p(kr["slot_point"]), _p(kr["covis_off"]),
+                    _p(kr["covis_kf"]), _p(kr["child_off"]), _p(kr["child_kf"]), _p(order))
+        check(lib().sivo_localmap_apply(self._h, C.byref(st)))
+        length = np.zeros(int(n_kf), np.int64)
+        length[:self.n_kf] = np.diff(self._slot_off)
+        if n_kr:
+            length[kr["idx"]] = np.diff(kr["slot_off"])
+        self._slot_off = np.concatenate([np.zeros(1, np.int64), np.cumsum(length)])
+        self.n_kf, self.n_points = int(n_kf), int(n_points)
+
+    def sizes(self):
+        """(n_kf, n_points, and the entries of obs_kf, slot_point, covis_kf, child_kf) of the handle."""
+        out = np.zeros(6, np.int64)
+        check(lib().sivo_localmap_sizes(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
+    def export(self):
+        """The handle's tables as a dict of arrays (n_kf and the twelve of TABLE_FIELDS): what create() would have to be given to make
+        this handle.  kf_order is the identity where the creator passed None."""
+        K, P, n_obs, n_slot, n_covis, n_child = self.sizes()
+        n = dict(obs_off=P + 1, obs_kf=n_obs, point_bad=P, kf_bad=K, slot_off=K + 1, slot_point=n_slot, covis_off=K + 1, covis_kf=n_covis,
+                 child_off=K + 1, child_kf=n_child, parent=K, kf_order=K)
+        t = {f: np.zeros(n[f], _DTYPE[f]) for f in TABLE_FIELDS}
+        st = _Tables(K, P, *[t[f].ctypes.data for f in TABLE_FIELDS])
+        check(lib().sivo_localmap_export(self._h, C.byref(st)))
+        return dict(t, n_kf=K)
 
     def set_bad(self, points=(), point_values=(), kfs=(), kf_values=()):
         """isBad() of the listed points / keyframes becomes the listed value."""
