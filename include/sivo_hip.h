@@ -1248,6 +1248,41 @@ int sivo_localmap_update(sivo_localmap_t map, int n_slots, const int32_t *frame_
                          int32_t *local_kf, int32_t *n_local_kf, int32_t *ref_kf, int point_capacity, int32_t *local_point,
                          int32_t *n_local_points, int32_t *counts);
 
+#define SIVO_BAWIN_SLOT_NONE (-1)      /* no slot of the keyframe holds the point (a stale observation) */
+#define SIVO_BAWIN_SLOT_AMBIGUOUS (-2) /* more than one slot does */
+
+/* The window of Optimizer::LocalBundleAdjustment (reference src/orbslam/Optimizer.cc:496-559,
+ * the vertices of :585-622 and the edges of :651-670) on the resident map.  DESIGN 3.6m.
+ * In: cand_kf[0] = pKF, cand_kf[1 ..] = pKF->GetVectorCovisibleKeyFrames() in its order
+ * (the handle's covis_kf, cut at ten, is not read); kf_local_pre / kf_fixed_pre / point_pre
+ * = the keyframes whose mnBALocalForKF / mnBAFixedForKF and the points whose mnBALocalForKF
+ * already equal pKF->mnId (each may be NULL with a count of 0).
+ * Out: local_kf = the candidates that are not bad, in order; cand_kf[0] is listed whatever
+ * its flag (:499).  local_point = over local_kf in order and their slots in order, the first
+ * occurrence of every point that is not null, not bad and not in point_pre (:516-533).
+ * fixed_kf = over local_point in order and their observation rows in order, the first
+ * occurrence of every keyframe that is neither a candidate nor in kf_local_pre nor in
+ * kf_fixed_pre, kept where it is not bad (:537-559).  Pose index j is local_kf[j] for
+ * j < n_local_kf and fixed_kf[j - n_local_kf] behind that.  For local point i the entries
+ * edge_off[i] .. edge_off[i + 1] are its observations in row order whose keyframe is not
+ * bad and has a pose index (:670): edge_pose = that index, edge_slot = the one slot s of
+ * the keyframe with slot_point[slot_off[k] + s] == p, or SIVO_BAWIN_SLOT_NONE /
+ * SIVO_BAWIN_SLOT_AMBIGUOUS (the handle does not store mObservations' idx: the caller
+ * resolves those two from its own map).  local_kf and fixed_kf hold kf_capacity entries
+ * each, local_point point_capacity, edge_off point_capacity + 1, edge_pose and edge_slot
+ * edge_capacity.  counts = n_local_kf, n_local_points, n_fixed_kf, n_edges: written on
+ * success and on SIVO_ERR_CAPACITY, where nothing else is written; entries past the counts
+ * are left as the caller had them.
+ * A null handle, n_cand < 1, an index out of range, a keyframe listed twice in cand_kf (the
+ * reference would add its vertex twice), a negative count or a NULL array with a non-zero
+ * count -> SIVO_ERR_INVALID_ARGUMENT before any device is touched.  The result depends on
+ * the handle's tables and this call's arguments alone. */
+int sivo_localmap_ba_window(sivo_localmap_t map, int n_cand, const int32_t *cand_kf, int n_kf_local_pre,
+                            const int32_t *kf_local_pre, int n_kf_fixed_pre, const int32_t *kf_fixed_pre, int n_point_pre,
+                            const int32_t *point_pre, int kf_capacity, int32_t *local_kf, int32_t *fixed_kf,
+                            int point_capacity, int32_t *local_point, int64_t *edge_off, int64_t edge_capacity,
+                            int32_t *edge_pose, int32_t *edge_slot, int64_t counts[4]);
+
 /* ===========================================================================
  * Place recognition: the bag-of-words vocabulary and the keyframe database —
  * DBoW2 as ORB-SLAM2 uses it (reference dependencies/DBoW2/DBoW2/TemplatedVocabulary.h,

@@ -6,6 +6,8 @@
 //     dev.Sync()                                              ... and ONE sivo_localmap_apply sends the rows of what was touched
 //     SIVO::UpdateLocalMap(dev, F, vpLocalKeyFrames, vpLocalMapPoints, pReferenceKF)
 //                                                             in place of UpdateLocalKeyFrames(); UpdateLocalPoints(); (:1092-1093)
+//     dev.BAWindow(pKF, window)                               the window of Optimizer::LocalBundleAdjustment (Optimizer.cc:496-559,
+//                                                             :651-670) from ONE sivo_localmap_ba_window, as pointers
 // as header-only templates.  UpdateLocalMap maps F.mvpMapPoints to indices, makes ONE call to sivo_localmap_update and writes back as the
 // reference does: the cleared slots of the frame (:1139), both vectors, mnTrackReferenceForFrame of every listed keyframe and point
 // (:1120, :1171, :1200, :1215, :1225), and pReferenceKF and F.mpReferenceKF where a keyframe had the most votes (:1231-1234).
@@ -13,7 +15,8 @@
 // KeyFrame, MapPoint and Frame are template parameters (SLAM data model, outside this library — SURVEY.md 8).  The members read, all the
 // reference's own: KeyFrame: GetMapPointMatches, GetVectorCovisibleKeyFrames (mvpOrderedConnectedKeyFrames; the first ten are used,
 // KeyFrame.cc:222-230), GetChildren, GetParent, isBad, mnTrackReferenceForFrame; MapPoint: GetObservations, isBad,
-// mnTrackReferenceForFrame; Frame: mnId, numSemanticKeys, mvpMapPoints, mpReferenceKF.
+// mnTrackReferenceForFrame; Frame: mnId, numSemanticKeys, mvpMapPoints, mpReferenceKF.  BAWindow reads and writes KeyFrame: mnId,
+// mnBALocalForKF, mnBAFixedForKF; MapPoint: mnBALocalForKF, GetIndexInKeyFrame.
 //
 // kf_order, the order in which the reference's std::map<KeyFrame *, int> walks (:1156), is std::less<KeyFrame *> over the pointers; the
 // children are listed as the std::set iterates.  A frame slot whose map point the handle does not know — one created after the last
@@ -249,6 +252,64 @@ class LocalMapDevice {
         mTouchedKFs.clear(); mTouchedPoints.clear();
     }
 
+    // What Optimizer::LocalBundleAdjustment has built when it starts to optimise (reference src/orbslam/Optimizer.cc:496-559, :651-670):
+    // lLocalKeyFrames, lLocalMapPoints and lFixedKFs in the reference's order — pose index j is localKFs[j], then fixedKFs[j - size] —
+    // and for local point i the edges edgeOff[i] .. edgeOff[i + 1]: the pose index of the observing keyframe and mObservations' idx.
+    struct Window {
+        std::vector<KeyFrameT *> localKFs, fixedKFs;
+        std::vector<MapPointT *> localPoints;
+        std::vector<int64_t> edgeOff;
+        std::vector<int32_t> edgePose;
+        std::vector<size_t> edgeIdx;
+    };
+
+    // The window of pKF from ONE sivo_localmap_ba_window on the map as the last Rebuild or Sync left it.  The candidates are pKF and its
+    // GetVectorCovisibleKeyFrames() in full; no premarks are passed, so the caller keeps pKF->mnId == 0 — the stamp every object starts
+    // with — on the host walk.  An edge whose slot the map cannot name (a stale observation, or a point in two slots of a keyframe) is
+    // resolved with pMP->GetIndexInKeyFrame(pKFi).  mnBALocalForKF of every candidate (:500, :508) and listed point (:528) and
+    // mnBAFixedForKF of every listed fixed keyframe (:553) are written.  pKF or a covisible the handle does not know — touched and not
+    // Synced — is an error.
+    void BAWindow(KeyFrameT *pKF, Window &w) {
+        std::lock_guard<std::mutex> lock(mMutex);                      // the whole call: it sees the map before a Sync or after it
+        if (!mHandle) throw std::invalid_argument("LocalMapDevice::BAWindow: Rebuild has not run");
+        std::vector<int32_t> cand(1, Known(pKF, "keyframe of the window"));
+        const std::vector<KeyFrameT *> vCovisibleKFs = pKF->GetVectorCovisibleKeyFrames();
+        for (KeyFrameT *pKFi : vCovisibleKFs) cand.push_back(Known(pKFi, "covisible of the window's keyframe"));
+        int64_t sizes[6];
+        localmap_detail::check(sivo_localmap_sizes(mHandle, sizes), "LocalMapDevice::BAWindow");
+        const size_t K = mvpKFs.size(), pointCap = (size_t)std::min<int64_t>((int64_t)mvpPoints.size(), mSlotOff.back()), edgeCap = (size_t)sizes[2];
+        // (the bounds no result exceeds, in buffers that stay: nothing of their size is allocated or cleared per call)
+        std::vector<int32_t> &localKf = mWinLocalKf, &fixedKf = mWinFixedKf, &localPoint = mWinLocalPoint, &edgePose = mWinEdgePose, &edgeSlot = mWinEdgeSlot;
+        if (localKf.size() < K) { localKf.resize(K); fixedKf.resize(K); }
+        if (localPoint.size() < pointCap) localPoint.resize(pointCap);
+        if (edgePose.size() < edgeCap) { edgePose.resize(edgeCap); edgeSlot.resize(edgeCap); }
+        if (mWinEdgeOff.size() < pointCap + 1) mWinEdgeOff.resize(pointCap + 1);
+        int64_t counts[4] = {0, 0, 0, 0};
+        localmap_detail::check(sivo_localmap_ba_window(mHandle, (int)cand.size(), cand.data(), 0, nullptr, 0, nullptr, 0, nullptr, (int)K, localKf.data(),
+                                                       fixedKf.data(), (int)pointCap, localPoint.data(), mWinEdgeOff.data(), (int64_t)edgeCap,
+                                                       edgePose.data(), edgeSlot.data(), counts),
+                               "LocalMapDevice::BAWindow");
+        const size_t nLocal = (size_t)counts[0], nPoints = (size_t)counts[1], nFixed = (size_t)counts[2], nEdges = (size_t)counts[3];
+        w.localKFs.clear(); w.fixedKFs.clear(); w.localPoints.clear();
+        for (size_t j = 0; j < nLocal; ++j) w.localKFs.push_back(mvpKFs[(size_t)localKf[j]]);
+        for (size_t j = 0; j < nFixed; ++j) w.fixedKFs.push_back(mvpKFs[(size_t)fixedKf[j]]);
+        for (size_t i = 0; i < nPoints; ++i) w.localPoints.push_back(mvpPoints[(size_t)localPoint[i]]);
+        w.edgeOff.assign(mWinEdgeOff.begin(), mWinEdgeOff.begin() + (std::ptrdiff_t)(nPoints + 1));
+        w.edgePose.assign(edgePose.begin(), edgePose.begin() + (std::ptrdiff_t)nEdges);
+        w.edgeIdx.assign(nEdges, 0);
+        for (size_t i = 0; i < nPoints; ++i)
+            for (int64_t e = w.edgeOff[i]; e < w.edgeOff[i + 1]; ++e) {
+                if (edgeSlot[(size_t)e] >= 0) { w.edgeIdx[(size_t)e] = (size_t)edgeSlot[(size_t)e]; continue; }
+                const size_t j = (size_t)edgePose[(size_t)e];
+                const int idx = w.localPoints[i]->GetIndexInKeyFrame(j < nLocal ? w.localKFs[j] : w.fixedKFs[j - nLocal]);
+                if (idx < 0) throw std::runtime_error("LocalMapDevice::BAWindow: the device map holds an observation its map point no longer has (touched and not Synced)");
+                w.edgeIdx[(size_t)e] = (size_t)idx;
+            }
+        for (int32_t k : cand) mvpKFs[(size_t)k]->mnBALocalForKF = pKF->mnId;          // (:500, :508)
+        for (MapPointT *pMP : w.localPoints) pMP->mnBALocalForKF = pKF->mnId;           // (:528)
+        for (KeyFrameT *pKFi : w.fixedKFs) pKFi->mnBAFixedForKF = pKF->mnId;            // (:553)
+    }
+
     // the index of a keyframe the handle knows (the caller holds mMutex or is the only thread)
     int32_t Known(KeyFrameT *pKF, const char *role) const {
         const auto it = mKFIndex.find(pKF);
@@ -265,6 +326,8 @@ class LocalMapDevice {
     std::mutex mMutex;                      // guards the maps above and the sets below
     std::set<KeyFrameT *> mTouchedKFs;
     std::set<MapPointT *> mTouchedPoints;
+    std::vector<int32_t> mWinLocalKf, mWinFixedKf, mWinLocalPoint, mWinEdgePose, mWinEdgeSlot;      // BAWindow's output buffers
+    std::vector<int64_t> mWinEdgeOff;
 };
 
 // In place of UpdateLocalKeyFrames(); UpdateLocalPoints(); (Tracking.cc:1092-1093).  Every keyframe and point of the handle is asked for

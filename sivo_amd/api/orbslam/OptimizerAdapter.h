@@ -24,8 +24,10 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
+#include "LocalMapAdapter.h"
 #include "Optimizer.h"
 
 #ifdef SIVO_HAVE_OPENCV
@@ -485,11 +487,50 @@ int PoseOptimization(FrameT *pFrame) {
     return inliers;
 }
 
-// void Optimizer::LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap)
-template <class KeyFrameT, class MapT>
-void LocalBundleAdjustment(KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap) {
-    using namespace optimizer_detail;
-    typedef typename std::remove_pointer<typename decltype(pKF->GetMapPointMatches())::value_type>::type MapPointT;
+namespace optimizer_detail {
+
+// What Optimizer::LocalBundleAdjustment hands to the optimiser (Optimizer.cc:496-755): the window's keyframes and points in the
+// reference's order, the vertices as arrays (local keyframes first, keyframe 0 of the map held fixed, then the fixed ones), one SivoEdge
+// per observation and the objects behind each edge.
+template <class KeyFrameT, class MapPointT>
+struct LocalBAProblem {
+    std::vector<KeyFrameT *> localKFs;          // lLocalKeyFrames
+    std::vector<MapPointT *> localPoints;       // lLocalMapPoints
+    std::map<KeyFrameT *, int> poseIndex;
+    std::vector<double> poses;
+    std::vector<uint8_t> fixedPose;
+    std::vector<double> points;
+    std::vector<SivoEdge> edges;
+    std::vector<KeyFrameT *> edgeKF;
+    std::vector<MapPointT *> edgeMP;
+
+    void add_pose(KeyFrameT *k, bool fixed) {                                    // (:585-622)
+        double p[12];
+        se3_from_cv(k->GetPose(), p);
+        poseIndex[k] = (int)fixedPose.size();
+        poses.insert(poses.end(), p, p + 12);
+        fixedPose.push_back(fixed ? 1 : 0);
+    }
+    void add_point(MapPointT *pMP) {                                             // (:655-656)
+        const cv::Mat Xw = pMP->GetWorldPos();
+        for (int r = 0; r < 3; ++r) points.push_back(Xw.at<float>(r, 0));
+    }
+    void add_edge(KeyFrameT *pKFi, MapPointT *pMP, size_t idx, int pose, int point) {       // (:668-755)
+        edges.push_back(observation(*pKFi, idx, pose, point));
+        edgeKF.push_back(pKFi); edgeMP.push_back(pMP);
+    }
+};
+
+template <class KeyFrameT>
+struct MapPointOf {
+    typedef typename std::remove_pointer<typename decltype(std::declval<KeyFrameT *>()->GetMapPointMatches())::value_type>::type type;
+};
+
+// The walk over the object graph (Optimizer.cc:496-559, :585-622, :651-670)
+template <class KeyFrameT>
+LocalBAProblem<KeyFrameT, typename MapPointOf<KeyFrameT>::type> gather_local_ba(KeyFrameT *pKF) {
+    typedef typename MapPointOf<KeyFrameT>::type MapPointT;
+    LocalBAProblem<KeyFrameT, MapPointT> P;
     // local keyframes: the current one and its covisible neighbours (:496-512)
     std::list<KeyFrameT *> lLocalKeyFrames;
     lLocalKeyFrames.push_back(pKF);
@@ -517,43 +558,63 @@ void LocalBundleAdjustment(KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap) {
             }
         }
     // vertices -> arrays (:577-618): local keyframes first (keyframe 0 of the map is held fixed), then the fixed ones
-    std::map<KeyFrameT *, int> poseIndex;
-    std::vector<double> poses;
-    std::vector<uint8_t> fixedPose;
-    auto add_pose = [&](KeyFrameT *k, bool fixed) {
-        double p[12];
-        se3_from_cv(k->GetPose(), p);
-        poseIndex[k] = (int)fixedPose.size();
-        poses.insert(poses.end(), p, p + 12);
-        fixedPose.push_back(fixed ? 1 : 0);
-    };
-    for (KeyFrameT *k : lLocalKeyFrames) add_pose(k, k->mnId == 0);
-    for (KeyFrameT *k : lFixedKFs) add_pose(k, true);
+    for (KeyFrameT *k : lLocalKeyFrames) P.add_pose(k, k->mnId == 0);
+    for (KeyFrameT *k : lFixedKFs) P.add_pose(k, true);
     // points and edges (:646-755)
-    std::vector<double> points;
-    std::vector<SivoEdge> edges;
-    std::vector<KeyFrameT *> edgeKF;
-    std::vector<MapPointT *> edgeMP;
     int pointIndex = 0;
     for (MapPointT *pMP : lLocalMapPoints) {
-        const cv::Mat Xw = pMP->GetWorldPos();
-        for (int r = 0; r < 3; ++r) points.push_back(Xw.at<float>(r, 0));
+        P.add_point(pMP);
         for (const auto &ob : pMP->GetObservations()) {
             KeyFrameT *pKFi = ob.first;
             if (pKFi->isBad()) continue;
-            const auto it = poseIndex.find(pKFi);
-            if (it == poseIndex.end()) continue;          // (bad keyframes never became vertices)
-            edges.push_back(observation(*pKFi, ob.second, it->second, pointIndex));
-            edgeKF.push_back(pKFi); edgeMP.push_back(pMP);
+            const auto it = P.poseIndex.find(pKFi);
+            if (it == P.poseIndex.end()) continue;        // (bad keyframes never became vertices)
+            P.add_edge(pKFi, pMP, ob.second, it->second, pointIndex);
         }
         ++pointIndex;
     }
+    P.localKFs.assign(lLocalKeyFrames.begin(), lLocalKeyFrames.end());
+    P.localPoints.assign(lLocalMapPoints.begin(), lLocalMapPoints.end());
+    return P;
+}
+
+// The same problem from the resident map: one LocalMapDevice::BAWindow, then the arrays by index — no list, no std::map lookup per
+// observation, no copy of an observation map.
+template <class KeyFrameT, class MapPointT>
+LocalBAProblem<KeyFrameT, MapPointT> gather_local_ba(LocalMapDevice<KeyFrameT, MapPointT> &dev, KeyFrameT *pKF) {
+    LocalBAProblem<KeyFrameT, MapPointT> P;
+    typename LocalMapDevice<KeyFrameT, MapPointT>::Window w;
+    dev.BAWindow(pKF, w);
+    const size_t nLocal = w.localKFs.size();
+    for (KeyFrameT *k : w.localKFs) P.add_pose(k, k->mnId == 0);
+    for (KeyFrameT *k : w.fixedKFs) P.add_pose(k, true);
+    P.edges.reserve(w.edgePose.size()); P.edgeKF.reserve(w.edgePose.size()); P.edgeMP.reserve(w.edgePose.size());
+    for (size_t i = 0; i < w.localPoints.size(); ++i) {
+        MapPointT *pMP = w.localPoints[i];
+        P.add_point(pMP);
+        for (int64_t e = w.edgeOff[i]; e < w.edgeOff[i + 1]; ++e) {
+            const size_t j = (size_t)w.edgePose[(size_t)e];
+            P.add_edge(j < nLocal ? w.localKFs[j] : w.fixedKFs[j - nLocal], pMP, w.edgeIdx[(size_t)e], (int)j, (int)i);
+        }
+    }
+    P.localKFs.swap(w.localKFs);
+    P.localPoints.swap(w.localPoints);
+    return P;
+}
+
+// The optimisation and what the reference writes back (Optimizer.cc:757-926)
+template <class KeyFrameT, class MapPointT, class MapT>
+void solve_local_ba(LocalBAProblem<KeyFrameT, MapPointT> &P, KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap) {
+    std::vector<double> &poses = P.poses, &points = P.points;
+    const std::vector<SivoEdge> &edges = P.edges;
+    const std::vector<KeyFrameT *> &edgeKF = P.edgeKF;
+    const std::vector<MapPointT *> &edgeMP = P.edgeMP;
     if (pbStopFlag && *pbStopFlag) return;                                       // :757-761
     const double intr[5] = {pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf};
     std::vector<uint8_t> erase;
     double cov[36];
     bool covOk = false;
-    Optimizer::LocalBundleAdjustment(poses, fixedPose, points, edges, intr, pbStopFlag, erase, /*covariancePose=*/0, cov, &covOk);
+    Optimizer::LocalBundleAdjustment(poses, P.fixedPose, points, edges, intr, pbStopFlag, erase, /*covariancePose=*/0, cov, &covOk);
 
     // vToErase (:824-858): the monocular edges in edge order, THEN the stereo ones; a map point's isBad() is read while the list
     // is built, i.e. before anything is erased (an erasure can turn a point bad: its later entries are still erased).  Both
@@ -567,18 +628,35 @@ void LocalBundleAdjustment(KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap) {
         edgeKF[e]->EraseMapPointMatch(edgeMP[e]);
         edgeMP[e]->EraseObservation(edgeKF[e]);
     }
-    for (KeyFrameT *k : lLocalKeyFrames) {                                       // :884-910
-        k->SetPose(cv_from_se3(poses.data() + 12 * (size_t)poseIndex[k]));
+    for (KeyFrameT *k : P.localKFs) {                                            // :884-910
+        k->SetPose(cv_from_se3(poses.data() + 12 * (size_t)P.poseIndex[k]));
         if (k->mnId == pKF->mnId && covOk) set_covariance(pKF, cov);
     }
-    pointIndex = 0;
-    for (MapPointT *pMP : lLocalMapPoints) {                                     // :912-925
+    int pointIndex = 0;
+    for (MapPointT *pMP : P.localPoints) {                                       // :912-925
         cv::Mat X(3, 1, CV_32F);
         for (int r = 0; r < 3; ++r) X.at<float>(r, 0) = (float)points[3 * (size_t)pointIndex + r];
         pMP->SetWorldPos(X);
         pMP->UpdateNormalAndDepth();
         ++pointIndex;
     }
+}
+
+}  // namespace optimizer_detail
+
+// void Optimizer::LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap)
+template <class KeyFrameT, class MapT>
+void LocalBundleAdjustment(KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap) {
+    auto P = optimizer_detail::gather_local_ba(pKF);
+    optimizer_detail::solve_local_ba(P, pKF, pbStopFlag, pMap);
+}
+
+// The same with the window built on the resident map (LocalMapAdapter.h) in place of the walk: dev holds the map as the last Rebuild or
+// Sync left it.  For pKF->mnId == 0 every object's initial stamp already equals the id; the host walk, which reads the stamps, runs.
+template <class KeyFrameT, class MapPointT, class MapT>
+void LocalBundleAdjustment(LocalMapDevice<KeyFrameT, MapPointT> &dev, KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap) {
+    auto P = pKF->mnId == 0 ? optimizer_detail::gather_local_ba(pKF) : optimizer_detail::gather_local_ba(dev, pKF);
+    optimizer_detail::solve_local_ba(P, pKF, pbStopFlag, pMap);
 }
 
 // void Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust) (Optimizer.cc:49-271)

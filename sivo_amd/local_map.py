@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import ERR_CAPACITY, SivoError, check, lib
 
 LDS_KF = 8192                                                                              # SIVO_COVIS_LDS_KF
 TABLE_FIELDS = ("obs_off", "obs_kf", "point_bad", "kf_bad", "slot_off", "slot_point", "covis_off", "covis_kf", "child_off", "child_kf",
@@ -45,6 +45,15 @@ class Result:
     def __init__(self, voted, slot_cleared, local_kf, ref_kf, local_points, counts):
         self.voted, self.slot_cleared, self.local_kf, self.ref_kf = voted, slot_cleared, local_kf, ref_kf
         self.local_points, self.counts = local_points, counts
+
+
+class WindowCapacity(SivoError):
+    """SIVO_ERR_CAPACITY of ba_window under explicit capacities; counts = (n_local_kf, n_local_points, n_fixed_kf, n_edges), what a
+    second call needs."""
+
+    def __init__(self, msg, counts):
+        super().__init__(ERR_CAPACITY, msg)
+        self.counts = counts
 
 
 class LocalMap:
@@ -164,6 +173,31 @@ class LocalMap:
                                          _p(cleared), kcap, _p(local_kf), C.byref(n_kf), C.byref(ref), pcap, _p(local_point), C.byref(n_pts),
                                          _p(counts)))
         return Result(bool(voted.value), cleared, local_kf[:n_kf.value] if voted.value else None, int(ref.value), local_point[:n_pts.value], counts)
+
+    def ba_window(self, cand_kf, kf_local_premarked=None, kf_fixed_premarked=None, point_premarked=None, *, kf_capacity=None,
+                  point_capacity=None, edge_capacity=None):
+        """The window of Optimizer::LocalBundleAdjustment (Optimizer.cc:496-559, :651-670).  cand_kf: pKF, then its covisibles in their
+        order; the premarked lists: the keyframes whose mnBALocalForKF / mnBAFixedForKF and the points whose mnBALocalForKF already equal
+        pKF's id.  Returns local_kf, fixed_kf, local_points, edge_off, edge_pose, edge_slot (sivo_localmap_ba_window of
+        include/sivo_hip.h).  The capacities default to what no result can exceed; a result beyond a given one raises WindowCapacity."""
+        ck = _a(cand_kf, np.int32)
+        kl, kx, pp = (_a(() if x is None else x, np.int32) for x in (kf_local_premarked, kf_fixed_premarked, point_premarked))
+        K, P, n_obs, n_slot = self.sizes()[:4]
+        kcap = K if kf_capacity is None else int(kf_capacity)
+        pcap = min(P, n_slot) if point_capacity is None else int(point_capacity)
+        ecap = n_obs if edge_capacity is None else int(edge_capacity)
+        local_kf, fixed_kf = np.zeros(max(kcap, 0), np.int32), np.zeros(max(kcap, 0), np.int32)
+        local_point, edge_off = np.zeros(max(pcap, 0), np.int32), np.zeros(max(pcap, 0) + 1, np.int64)
+        edge_pose, edge_slot = np.zeros(max(ecap, 0), np.int32), np.zeros(max(ecap, 0), np.int32)
+        counts = np.zeros(4, np.int64)
+        rc = lib().sivo_localmap_ba_window(self._h, len(ck), _p(ck), len(kl), _p(kl), len(kx), _p(kx), len(pp), _p(pp), kcap, _p(local_kf),
+                                           _p(fixed_kf), pcap, _p(local_point), edge_off.ctypes.data, ecap, _p(edge_pose), _p(edge_slot),
+                                           counts.ctypes.data)
+        if rc == ERR_CAPACITY:
+            raise WindowCapacity(lib().sivo_last_error().decode(errors="replace"), tuple(int(v) for v in counts))
+        check(rc)
+        nl, npt, nf, ne = (int(v) for v in counts)
+        return local_kf[:nl], fixed_kf[:nf], local_point[:npt], edge_off[:npt + 1], edge_pose[:ne], edge_slot[:ne]
 
     def close(self):
         if self._h:
