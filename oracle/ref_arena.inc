@@ -36,6 +36,10 @@ void arena_end() {
 
 void *operator new(size_t n) { return arena_on ? arena_alloc(n) : std::malloc(n ? n : 1); }
 void *operator new[](size_t n) { return arena_on ? arena_alloc(n) : std::malloc(n ? n : 1); }
+void *operator new(size_t n, const std::nothrow_t &) noexcept { return arena_on ? arena_alloc(n) : std::malloc(n ? n : 1); }
+void *operator new[](size_t n, const std::nothrow_t &) noexcept { return arena_on ? arena_alloc(n) : std::malloc(n ? n : 1); }
+void operator delete(void *p, const std::nothrow_t &) noexcept { if (p && !in_arena(p)) std::free(p); }
+void operator delete[](void *p, const std::nothrow_t &) noexcept { if (p && !in_arena(p)) std::free(p); }
 void operator delete(void *p) noexcept { if (p && !in_arena(p)) std::free(p); }
 void operator delete[](void *p) noexcept { if (p && !in_arena(p)) std::free(p); }
 void operator delete(void *p, size_t) noexcept { if (p && !in_arena(p)) std::free(p); }

@@ -41,6 +41,7 @@ class Matrix {
     T &operator()(int i) { return v_[(size_t)i]; }
     const T &operator()(int i) const { return v_[(size_t)i]; }
 
+    Matrix &matrix() { return *this; }
     Matrix &operator*=(T s) { for (T &x : v_) x *= s; return *this; }
     static Matrix Zero() { return Matrix(); }
     static Matrix Identity() {
@@ -214,6 +215,7 @@ Matrix<T, R1, C1> operator-(const Matrix<T, R1, C1> &a, const Matrix<T, R2, C2> 
 typedef Matrix<double, 2, 2> Matrix2d;
 typedef Matrix<double, 3, 3> Matrix3d;
 typedef Matrix<double, 3, 1> Vector3d;
+typedef Matrix<double, 4, 4> Matrix4d;
 typedef Matrix<double, Dynamic, Dynamic> MatrixXd;
 
 class Affine3d {
@@ -222,6 +224,18 @@ class Affine3d {
     Vector3d translation_;
     Vector3d translation() const { return translation_; }
     Matrix3d rotation() const { return linear_; }
+    // `T.matrix() = M` with a 4 x 4 M: the upper 3 x 4 is taken (Tracking.cc:718)
+    struct MatrixRef {
+        Affine3d *t;
+        MatrixRef &operator=(const Matrix4d &m) {
+            for (int i = 0; i < 3; ++i) {
+                for (int j = 0; j < 3; ++j) t->linear_(i, j) = m(i, j);
+                t->translation_(i) = m(i, 3);
+            }
+            return *this;
+        }
+    };
+    MatrixRef matrix() { return MatrixRef{this}; }
 };
 
 }  // namespace Eigen

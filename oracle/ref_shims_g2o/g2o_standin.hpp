@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <memory>
 #include <vector>
@@ -335,6 +336,7 @@ class SparseOptimizer {
     bool addVertex(OptimizableGraph::Vertex *v) {
         if (vertices_.count(v->id())) return false;
         vertices_[v->id()] = v;
+        inserted_.push_back(v);
         return true;
     }
     bool removeVertex(OptimizableGraph::Vertex *v) {
@@ -344,6 +346,8 @@ class SparseOptimizer {
             if (uses) { delete edges_[i]; edges_.erase(edges_.begin() + (long)i); } else ++i;
         }
         vertices_.erase(v->id());
+        for (size_t i = 0; i < inserted_.size(); ++i)
+            if (inserted_[i] == v) { inserted_.erase(inserted_.begin() + (long)i); break; }
         delete v;
         return true;
     }
@@ -363,10 +367,15 @@ class SparseOptimizer {
         return it == vertices_.end() ? nullptr : it->second;
     }
     const std::vector<OptimizableGraph::Edge *> &edges() const { return edges_; }
+    const std::vector<OptimizableGraph::Vertex *> &verticesInInsertionOrder() const { return inserted_; }
+    // The recording mode (oracle/ref_bawindow_driver.cpp): a hook that is handed the graph at initializeOptimization, before anything is
+    // solved; it may throw to leave the optimisation there.  Empty in every other program.
+    static std::function<void(const SparseOptimizer &)> &recordHook() { static std::function<void(const SparseOptimizer &)> h; return h; }
 
     // active set = the edges of that level; free pose vertices get their Hessian index in ascending id order
     bool initializeOptimization(int level = 0) {
         active_level_ = level;
+        if (recordHook()) recordHook()(*this);
         return true;
     }
     int optimize(int iterations) {
@@ -444,6 +453,7 @@ class SparseOptimizer {
  private:
     std::map<int, OptimizableGraph::Vertex *> vertices_;
     std::vector<OptimizableGraph::Edge *> edges_;
+    std::vector<OptimizableGraph::Vertex *> inserted_;       // the vertices in the order addVertex took them
     OptimizationAlgorithm *algorithm_ = nullptr;
     bool *stop_ = nullptr;
     int active_level_ = 0;

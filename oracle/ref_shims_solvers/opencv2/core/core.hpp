@@ -77,6 +77,12 @@ class Mat : public MatCore {
             for (int c = 0; c < cols; ++c) out.at<float>(r, c) = depth() == CV_64F ? (float)MatCore::at<double>(r, c) : MatCore::at<float>(r, c);
         dst = Mat(out);
     }
+    // Mat::resize(n): n rows, the rows that stay keep their values (Tracking.cc:85, a 4 x 1 matrix that becomes 5 x 1)
+    void resize(size_t nrows) {
+        MatCore out(MatCore::zeros((int)nrows, cols, type()));
+        for (int r = 0; r < rows && r < (int)nrows; ++r) std::memcpy(out.ptr(r), ptr(r), (size_t)cols * elemSize());
+        MatCore::operator=(out);
+    }
 
  private:
     void write(const MatCore &v) {

@@ -29,10 +29,11 @@ def GetVectorCovisibleKeyFrames(pKF):                                # KeyFrame.
 
 class Window:
     """lLocalKeyFrames, lLocalMapPoints, lFixedKFs, the pose vertices in the order they are added, and per local point its edges as
-    (pKFi, idx) in the order they are added."""
+    (pKFi, idx) in the order they are added.  `stray` holds, per local point, the edges the reference ties to a POINT vertex: (the local
+    point whose vertex the id lookup found, pKFi, idx) — see LocalBundleAdjustment; they are no part of `edges`."""
 
     def __init__(self):
-        self.lLocalKeyFrames, self.lLocalMapPoints, self.lFixedKFs, self.vertices, self.edges = [], [], [], [], []
+        self.lLocalKeyFrames, self.lLocalMapPoints, self.lFixedKFs, self.vertices, self.edges, self.stray = [], [], [], [], [], []
 
 
 def LocalBundleAdjustment(pKF):
@@ -70,14 +71,21 @@ def LocalBundleAdjustment(pKF):
     for pKFi in w.lFixedKFs:                                        # :608-609
         w.vertices.append(pKFi)                                     # :612-618
 
+    maxKFid = max([0] + [v.mnId for v in w.vertices])               # :577, :602-604, :619-621
+    by_id = {v.mnId: v for v in w.vertices}                         # optimizer.vertex(id) looks an id up among ALL vertices
     for pMP in w.lLocalMapPoints:                                   # :651-653
+        by_id.setdefault(pMP.mnId + maxKFid + 1, pMP)               # :657-660 (addVertex refuses an id that is taken)
         observations = pMP.GetObservations()                        # :662-663
-        row = []
+        row, stray = [], []
         for pKFi, idx in observations:                              # :666-668
             if not pKFi.isBad():                                    # :670
-                if any(v is pKFi for v in w.vertices):              # (optimizer.vertex(pKFi->mnId) is null otherwise: no edge is added)
+                v = by_id.get(pKFi.mnId)                            # :687, :726: by the keyframe's id, not by the keyframe
+                if v is pKFi:
                     row.append((pKFi, idx))
-        w.edges.append(row)
+                elif v is not None:                                 # a keyframe without a pose vertex whose id a point vertex carries: the
+                    stray.append((v, pKFi, idx))                    # reference adds an edge between two point vertices, which no solve survives
+        w.edges.append(row)                                         # (optimizer.vertex() is null otherwise: addEdge refuses the edge)
+        w.stray.append(stray)
     return w
 
 
