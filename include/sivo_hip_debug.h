@@ -53,6 +53,14 @@ int sivo_debug_conv_cls_h3_dev(int T, int Cin, int C, int H, int W, const float 
  * [3] conv7_h3_kernel; the smallest request of each, 0 = not launched.  163840 = nobody else's LDS fits on that CU. */
 int sivo_debug_lds_claims(uint32_t out[4], int reset);
 
+/* sivo_local_ba_opts with the iteration budgets of its two g2o optimize() calls as arguments (the product's are 5 and 10): the same
+ * function of libsivo_hip.so runs.  A budget below the product's is the schedule that a pbStopFlag raised at an iteration boundary
+ * leaves (g2o stops before the next iteration), reached without a second thread.  Every other argument as sivo_local_ba_opts. */
+int sivo_debug_local_ba_budget(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
+                               const SivoEdge *edges, int64_t n_edges, const double intr[5], const volatile uint8_t *stop_flag,
+                               uint8_t *outlier, int cov_pose, double *cov, int *cov_ok, int *iterations, int *trials,
+                               int it_first, int it_second, const SivoBaOptions *opts);
+
 #ifdef __cplusplus
 }
 #endif

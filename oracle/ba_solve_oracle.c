@@ -154,7 +154,10 @@ typedef struct {
     double *Hpp_last;            /* 36 per free pose: Hpp blocks of the last buildSystem */
     const volatile int *stop;
     const volatile uint8_t *stop8;   /* the same as one byte (the reference's `bool *pbStopFlag`, read while the solve runs) */
+    /* optional trace: `err` as every active_errors() left it, with what that evaluation was (ORC_TRACE_*) */
+    double *trace_err; int32_t *trace_kind; int trace_cap, trace_n;
 } Problem;
+enum { ORC_TRACE_CALL_START = 0, ORC_TRACE_LINEARISATION = 1, ORC_TRACE_TRIAL_REJECTED = 2, ORC_TRACE_TRIAL_ACCEPTED = 3 };
 #define STOPPED(p) (((p)->stop && *(p)->stop) || ((p)->stop8 && *(p)->stop8))
 
 static double active_errors(Problem *p) {
@@ -171,6 +174,16 @@ static double active_errors(Problem *p) {
     return chi;
 }
 
+/* one trace record (counted even when the caller's arrays are full, so that the caller sees an overflow) */
+static void trace_push(Problem *p, int kind) {
+    if (!p->trace_kind) return;
+    if (p->trace_n < p->trace_cap) {
+        p->trace_kind[p->trace_n] = kind;
+        memcpy(p->trace_err + (size_t)p->trace_n * 3 * (size_t)p->nE, p->err, (size_t)p->nE * 24);
+    }
+    ++p->trace_n;
+}
+
 /* g2o::SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg; returns iterations run */
 static int lm_optimize(Problem *p, int iterations, int *trials_out) {
     const int nF = p->nF, n6 = 6 * nF, nX = p->points_fixed ? 0 : p->nX;
@@ -185,6 +198,7 @@ static int lm_optimize(Problem *p, int iterations, int *trials_out) {
     for (; it < iterations; ++it) {
         if (STOPPED(p)) break;
         double current = active_errors(p);
+        trace_push(p, it == 0 ? ORC_TRACE_CALL_START : ORC_TRACE_LINEARISATION);
         /* buildSystem */
         memset(Hpp, 0, (size_t)(nF ? nF : 1) * 36 * 8); memset(bp, 0, (size_t)(n6 ? n6 : 1) * 8);
         memset(Hll, 0, (size_t)(nX ? nX : 1) * 72); memset(bl, 0, (size_t)(nX ? nX : 1) * 24);
@@ -305,7 +319,9 @@ static int lm_optimize(Problem *p, int iterations, int *trials_out) {
                 alpha = fmin(alpha, 2. / 3.);
                 lambda *= fmax(1. / 3., alpha);
                 ni = 2; current = temp;
+                trace_push(p, ORC_TRACE_TRIAL_ACCEPTED);
             } else {
+                trace_push(p, ORC_TRACE_TRIAL_REJECTED);
                 lambda *= ni; ni *= 2;
                 memcpy(p->poses, bk_pose, (size_t)p->nP * 96);
                 if (nX) memcpy(p->points, bk_pts, (size_t)p->nX * 24);
@@ -390,9 +406,16 @@ int orc_pose_optimize(const double *pose0, const double *points, const OrcEdge *
  * stopped, edges with chi2 > 5.991 (mono) / 7.815 (stereo) or non-positive depth go to level 1 and every kernel
  * is dropped; optimize(10); final classification -> outlier[] (the observations the caller erases).  poses and
  * points are updated in place.  cov (36) = marginal block of pose `cov_pose` (ignored when < 0 or fixed). */
-int orc_local_ba(double *poses, const uint8_t *fixed, int nP, double *points, int nX, const OrcEdge *edges, int64_t nE,
-                 const double *intr, const int *stop, uint8_t *outlier, int cov_pose, double *cov, int *cov_ok,
-                 int *iters, int *trials) {
+/* The same with the iteration budgets of the two optimize() calls as arguments — (5, 10) is the reference's; a smaller one is what g2o
+ * runs when pbStopFlag goes up at an iteration boundary — and optional outputs (null: not wanted): level_out, the level flags after
+ * the first classification; chi2_out, the chi2 of every edge as g2o's edges hold it at the end (an edge at level 1 keeps the value that
+ * excluded it); depth_ok_out, isDepthPositive at the final estimates; and the trace: err (3 per edge) after every
+ * computeActiveErrors() in trace_err[k], what that evaluation was in trace_kind[k] (0 the first linearisation of a call, 1 a later
+ * one, 2 a rejected trial, 3 an accepted one), at most trace_cap records written, *trace_n the number there were. */
+int orc_local_ba_budget(double *poses, const uint8_t *fixed, int nP, double *points, int nX, const OrcEdge *edges, int64_t nE,
+                        const double *intr, const int *stop, uint8_t *outlier, int cov_pose, double *cov, int *cov_ok,
+                        int *iters, int *trials, int it_first, int it_second, uint8_t *level_out, double *chi2_out,
+                        uint8_t *depth_ok_out, double *trace_err, int32_t *trace_kind, int trace_cap, int *trace_n) {
     Problem p;
     memset(&p, 0, sizeof p);
     p.poses = poses; p.fixed = fixed; p.nP = nP; p.points = points; p.nX = nX; p.edges = edges; p.nE = nE; p.intr = intr;
@@ -400,9 +423,13 @@ int orc_local_ba(double *poses, const uint8_t *fixed, int nP, double *points, in
     p.level = calloc((size_t)(nE ? nE : 1), 1); p.robust = malloc((size_t)(nE ? nE : 1)); memset(p.robust, 1, (size_t)nE);
     p.err = calloc((size_t)(nE ? nE : 1) * 3, 8); p.slot = malloc((size_t)(nP ? nP : 1) * sizeof(int));
     p.stop = (const volatile int *)stop;
+    if (trace_err && trace_kind) { p.trace_err = trace_err; p.trace_kind = trace_kind; p.trace_cap = trace_cap; }
     int nF = 0;
     for (int i = 0; i < nP; ++i) p.slot[i] = fixed[i] ? -1 : nF++;
     p.nF = nF; p.Hpp_last = calloc((size_t)(nF ? nF : 1) * 36, 8);
+    if (level_out) memset(level_out, 0, (size_t)nE);
+    if (chi2_out) memset(chi2_out, 0, (size_t)nE * 8);
+    if (depth_ok_out) memset(depth_ok_out, 0, (size_t)nE);
     if (iters) *iters = 0;
     if (trials) *trials = 0;
     if (cov_ok) *cov_ok = 0;
@@ -410,7 +437,7 @@ int orc_local_ba(double *poses, const uint8_t *fixed, int nP, double *points, in
     if (stop && *stop) goto done;
     {
         int tr = 0;
-        int n = lm_optimize(&p, 5, &tr);
+        int n = lm_optimize(&p, it_first, &tr);
         if (!(stop && *stop)) {
             for (int64_t e = 0; e < nE; ++e) {
                 const double *er = p.err + 3 * e;
@@ -421,18 +448,21 @@ int orc_local_ba(double *poses, const uint8_t *fixed, int nP, double *points, in
                 if (c2 > (edges[e].stereo ? 7.815 : 5.991) || !dok) p.level[e] = 1;
                 p.robust[e] = 0;
             }
-            n += lm_optimize(&p, 10, &tr);
+            if (level_out) memcpy(level_out, p.level, (size_t)nE);
+            n += lm_optimize(&p, it_second, &tr);
         }
         if (iters) *iters = n;
         if (trials) *trials = tr;
-        if (outlier)
+        if (outlier || chi2_out || depth_ok_out)
             for (int64_t e = 0; e < nE; ++e) {
                 const double *er = p.err + 3 * e;
                 const double c2 = (er[0] * er[0] + er[1] * er[1] + er[2] * er[2]) * edges[e].inv_sigma2;
                 int dok;
                 double tmp[3];
                 edge_eval(poses + 12 * edges[e].pose, points + 3 * edges[e].point, &edges[e], intr, tmp, 0, 0, &dok);
-                outlier[e] = (c2 > (edges[e].stereo ? 7.815 : 5.991) || !dok);
+                if (outlier) outlier[e] = (c2 > (edges[e].stereo ? 7.815 : 5.991) || !dok);
+                if (chi2_out) chi2_out[e] = c2;
+                if (depth_ok_out) depth_ok_out[e] = (uint8_t)dok;
             }
         if (cov && cov_pose >= 0 && cov_pose < nP && p.slot[cov_pose] >= 0) {
             const int ok = inv6_spd(p.Hpp_last + 36 * p.slot[cov_pose], cov);
@@ -440,8 +470,17 @@ int orc_local_ba(double *poses, const uint8_t *fixed, int nP, double *points, in
         }
     }
 done:
+    if (trace_n) *trace_n = p.trace_n;
     free(p.level); free(p.robust); free(p.err); free(p.slot); free(p.Hpp_last);
     return 0;
+}
+
+/* with the reference's budgets: optimize(5) (:763-764), optimize(10) (:820-821) */
+int orc_local_ba(double *poses, const uint8_t *fixed, int nP, double *points, int nX, const OrcEdge *edges, int64_t nE,
+                 const double *intr, const int *stop, uint8_t *outlier, int cov_pose, double *cov, int *cov_ok,
+                 int *iters, int *trials) {
+    return orc_local_ba_budget(poses, fixed, nP, points, nX, edges, nE, intr, stop, outlier, cov_pose, cov, cov_ok, iters, trials,
+                               5, 10, 0, 0, 0, 0, 0, 0, 0);
 }
 
 /* One g2o optimize(iterations) call on arrays (what Optimizer::BundleAdjustment, Optimizer.cc:49-271, runs with

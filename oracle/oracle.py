@@ -357,19 +357,36 @@ def pose_optimize(pose0, points, edges, intr):
             "iterations": iters.value, "trials": trials.value}
 
 
-def local_ba(poses, fixed, points, edges, intr, cov_pose=-1, stop=False):
-    """Optimizer::LocalBundleAdjustment (Optimizer.cc:757-926) on arrays; returns updated copies."""
+TRACE_KINDS = ("call_start", "linearisation", "trial_rejected", "trial_accepted")      # ORC_TRACE_* of ba_solve_oracle.c
+
+
+def local_ba(poses, fixed, points, edges, intr, cov_pose=-1, stop=False, budget=(5, 10), trace=False):
+    """Optimizer::LocalBundleAdjustment (Optimizer.cc:757-926) on arrays; returns updated copies.  budget: the iterations of the two
+    optimize() calls (the reference's 5 and 10; fewer is what g2o runs when pbStopFlag goes up at an iteration boundary).  Per edge:
+    `level`, the flags after the first classification; `chi2`, as g2o's edges hold it at the end (a leveled edge keeps the value that
+    excluded it); `depth_ok`.  trace=True adds `trace`, a list of (kind, err) — err (nE, 3) as every computeActiveErrors() left it,
+    kind one of TRACE_KINDS."""
     poses = np.array(poses, np.float64).reshape(-1, 12).copy(); points = np.array(points, np.float64).reshape(-1, 3).copy()
     fixed = np.ascontiguousarray(fixed, np.uint8); edges = np.ascontiguousarray(edges, EDGE_DTYPE)
     intr = np.ascontiguousarray(intr, np.float64)
     nE = edges.shape[0]
+    it_first, it_second = (int(b) for b in budget)
     outlier = np.zeros(nE, np.uint8); cov = np.zeros((6, 6))
+    level = np.zeros(nE, np.uint8); chi2 = np.zeros(nE); depth_ok = np.zeros(nE, np.uint8)
     cov_ok = C.c_int(0); iters = C.c_int(0); trials = C.c_int(0); stop_flag = C.c_int(1 if stop else 0)
-    lib().orc_local_ba(_p(poses, c_f64p), _p(fixed, c_u8p), poses.shape[0], _p(points, c_f64p), points.shape[0],
-                       edges.ctypes.data_as(C.c_void_p), C.c_int64(nE), _p(intr, c_f64p), C.byref(stop_flag),
-                       _p(outlier, c_u8p), cov_pose, _p(cov, c_f64p), C.byref(cov_ok), C.byref(iters), C.byref(trials))
-    return {"poses": poses, "points": points, "outlier": outlier, "cov": cov, "cov_ok": bool(cov_ok.value),
-            "iterations": iters.value, "trials": trials.value}
+    cap = 11 * (it_first + it_second) if trace else 0          # an iteration evaluates once and tries at most ten times
+    t_err = np.zeros((max(cap, 1), nE, 3)); t_kind = np.zeros(max(cap, 1), np.int32); t_n = C.c_int(0)
+    lib().orc_local_ba_budget(_p(poses, c_f64p), _p(fixed, c_u8p), poses.shape[0], _p(points, c_f64p), points.shape[0],
+                              edges.ctypes.data_as(C.c_void_p), C.c_int64(nE), _p(intr, c_f64p), C.byref(stop_flag),
+                              _p(outlier, c_u8p), cov_pose, _p(cov, c_f64p), C.byref(cov_ok), C.byref(iters), C.byref(trials),
+                              it_first, it_second, _p(level, c_u8p), _p(chi2, c_f64p), _p(depth_ok, c_u8p),
+                              _p(t_err, c_f64p) if trace else None, _p(t_kind, c_i32p) if trace else None, cap, C.byref(t_n))
+    out = {"poses": poses, "points": points, "outlier": outlier, "cov": cov, "cov_ok": bool(cov_ok.value),
+           "iterations": iters.value, "trials": trials.value, "level": level, "chi2": chi2, "depth_ok": depth_ok}
+    if trace:
+        assert t_n.value <= cap
+        out["trace"] = [(TRACE_KINDS[t_kind[k]], t_err[k]) for k in range(t_n.value)]
+    return out
 
 
 def ba_optimize(poses, fixed, points, edges, intr, iterations, level=None, robust=None,

@@ -272,6 +272,7 @@ DEBUG_SIGNATURES = {
     "sivo_debug_conv3_h3_pk_dev": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _i, C.POINTER(_d), C.POINTER(_i)],
     "sivo_debug_lds_claims": [_vp, _i],
     "sivo_debug_conv_cls_h3_dev": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _i, C.POINTER(_d)],
+    "sivo_debug_local_ba_budget": [_vp, _vp, _i, _vp, _i, _vp, _i64, C.POINTER(_d), _vp, _vp, _i, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _i, _vp],
 }
 DBG_PATH = os.path.join(_HERE, "libsivo_hip_dbg.so")
 

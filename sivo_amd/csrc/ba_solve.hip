@@ -642,7 +642,7 @@ __global__ __launch_bounds__(BA_T) void ba_edge_kernel(BaDev d, double *partial 
     double v[1] = {0.0};
     if (e < d.nE) {
         if (d.level[e]) {
-            es.rchi[e] = 0.0;
+            es.rchi[e] = 0.0;                       // (err stays: classify(as_level) left the error that excluded the edge in both sets)
         } else {
             const SivoEdge ed = d.edges[e];
             double er[3], jp[18], jx[9];
@@ -1378,15 +1378,26 @@ __global__ void ba_pose_only_system_kernel(BaDev d) {
 }
 
 // final chi2 / depth test of LocalBundleAdjustment (:774-821, :826-858)
-__global__ __launch_bounds__(BA_T) void ba_classify_kernel(BaDev d, const double *poses, const double *points, uint8_t *out) {
+// to_level: `out` becomes the edges' levels.  An edge that goes to level 1 is written by no later evaluation, in either set, while g2o's
+// edge keeps the ONE error vector that excluded it and the final test reads that (:837 / :853).  Which set the final test reads depends
+// on the parity of the accepted trials of the second optimize(): the errors of every edge leveled here go into the other set as well, so
+// that a leveled edge's error is the same in both and stays the one that excluded it.
+__global__ __launch_bounds__(BA_T) void ba_classify_kernel(BaDev d, const double *poses, const double *points, uint8_t *out, int to_level) {
     const int64_t e = (int64_t)blockIdx.x * BA_T + threadIdx.x;
     if (e >= d.nE) return;
     const SivoEdge ed = d.edges[e];
-    const double *er = (d.lm->last_set ? d.sets[1].err : d.sets[0].err) + 3 * e;          // the errors of the last evaluation, as g2o's edges hold them
-    const double c2 = (er[0] * er[0] + er[1] * er[1] + er[2] * er[2]) * ed.inv_sigma2;
+    const int set = d.lm->last_set;
+    const double *er = (set ? d.sets[1].err : d.sets[0].err) + 3 * e;          // the errors of the last evaluation, as g2o's edges hold them
+    const double e0 = er[0], e1 = er[1], e2 = er[2];
+    const double c2 = (e0 * e0 + e1 * e1 + e2 * e2) * ed.inv_sigma2;
     const double *R = poses + 12 * (int64_t)ed.pose, *X = points + 3 * (int64_t)ed.point;
     const double z = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + R[11];
-    out[e] = (c2 > (ed.stereo ? 7.815 : 5.991)) || !(z > 0.0);
+    const bool flag = (c2 > (ed.stereo ? 7.815 : 5.991)) || !(z > 0.0);
+    out[e] = flag;
+    if (to_level && flag) {
+        double *other = (set ? d.sets[0].err : d.sets[1].err) + 3 * e;
+        other[0] = e0; other[1] = e1; other[2] = e2;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1579,12 +1590,13 @@ class BaSolver {
     }
 
     // chi2 / depth classification at the current estimates using the error vectors g2o would hold.  as_level: the flags become the
-    // edges' levels (the kernel does not read the flags it replaces) and every robust kernel is dropped (:774-817); otherwise they are
-    // what download() hands out as `outlier`
+    // edges' levels (the kernel does not read the flags it replaces), the errors of the edges it levels are kept in both per-edge sets,
+    // and every robust kernel is dropped (:774-817); otherwise they are what download() hands out as `outlier`
     void classify(bool as_level) {
         if (!nE_) return;
         hipLaunchKernelGGL(ba_classify_kernel, dim3((unsigned)cdiv64(nE_, BA_T)), dim3(BA_T), 0, ctx_.stream, d_,
-                           (const double *)d_.poses[cur_], (const double *)d_.points[cur_], as_level ? const_cast<uint8_t *>(d_.level) : flags_);
+                           (const double *)d_.poses[cur_], (const double *)d_.points[cur_], as_level ? const_cast<uint8_t *>(d_.level) : flags_,
+                           as_level ? 1 : 0);
         SIVO_HIP(hipGetLastError());
         if (as_level) SIVO_HIP(hipMemsetAsync(const_cast<uint8_t *>(d_.robust), 0, (size_t)nE_, ctx_.stream));
     }
@@ -1696,8 +1708,19 @@ extern "C" int sivo_local_ba_opts(double *poses, const uint8_t *pose_fixed, int 
                                   const SivoEdge *edges, int64_t n_edges, const double intr[5], const volatile uint8_t *stop_flag,
                                   uint8_t *outlier, int cov_pose, double *cov, int *cov_ok, int *iterations, int *trials,
                                   const SivoBaOptions *opts) {
+    return local_ba_budget(poses, pose_fixed, n_poses, points, n_points, edges, n_edges, intr, stop_flag, outlier, cov_pose, cov, cov_ok,
+                           iterations, trials, 5, 10, opts);                  // optimize(5) (:763-764), optimize(10) (:820-821)
+}
+
+// LocalBundleAdjustment with the iteration budgets of its two optimize() calls as arguments (common.hpp).  The reference's are (5, 10);
+// a smaller budget is what g2o runs when pbStopFlag goes up at an iteration boundary, which sivo_debug_local_ba_budget lets a test
+// reach without a second thread.
+int sivo::local_ba_budget(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points, const SivoEdge *edges,
+                          int64_t n_edges, const double intr[5], const volatile uint8_t *stop_flag, uint8_t *outlier, int cov_pose,
+                          double *cov, int *cov_ok, int *iterations, int *trials, int it_first, int it_second, const SivoBaOptions *opts) {
     return guarded([&] {
         if (!poses || !intr || (n_edges && !edges) || (n_points && !points)) throw std::invalid_argument("null argument");
+        if (it_first < 0 || it_second < 0) throw std::invalid_argument("negative iteration count");
         const int solver = ba_solver_option(opts);
         require_device();
         if (iterations) *iterations = 0;
@@ -1708,10 +1731,10 @@ extern "C" int sivo_local_ba_opts(double *poses, const uint8_t *pose_fixed, int 
         BaSolver s(poses, pose_fixed, n_poses, points, n_points, false, edges, n_edges, nullptr, nullptr, intr,
                    (double)std::sqrt(5.991f), (double)std::sqrt(7.815f), solver);      // const float thHuber = sqrt(5.991f) (:646-647)
         int tr = 0;
-        int n = s.optimize(5, stop_flag, &tr);                                // :763-764
+        int n = s.optimize(it_first, stop_flag, &tr);                         // :763-764
         if (!(stop_flag && *stop_flag)) {                                     // bDoMore (:766-772)
             s.classify(true);                                                 // :774-817
-            n += s.optimize(10, stop_flag, &tr);                              // :820-821
+            n += s.optimize(it_second, stop_flag, &tr);                       // :820-821
         }
         s.classify(false);                                                    // :824-858
         const int cov_slot = cov ? s.free_slot(cov_pose) : -1;

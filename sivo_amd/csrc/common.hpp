@@ -121,6 +121,12 @@ enum { LDS_CLAIM_GEMM_H3 = 0, LDS_CLAIM_CONV3_H3, LDS_CLAIM_CLS_H3, LDS_CLAIM_CO
 void lds_claim_note(int kernel, size_t bytes_per_cu);
 void lds_claims(uint32_t out[LDS_CLAIM_KERNELS], bool reset);        // 0 = no launch since the last reset
 
+// sivo_local_ba_opts (ba_solve.hip) with the iteration budgets of its two optimize() calls as arguments — the product passes the
+// reference's (5, 10).  sivo_debug_local_ba_budget passes others: the schedule a stop flag raised at an iteration boundary leaves.
+int local_ba_budget(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points, const SivoEdge *edges,
+                    int64_t n_edges, const double intr[5], const volatile uint8_t *stop_flag, uint8_t *outlier, int cov_pose,
+                    double *cov, int *cov_ok, int *iterations, int *trials, int it_first, int it_second, const SivoBaOptions *opts);
+
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

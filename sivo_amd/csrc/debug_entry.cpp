@@ -433,3 +433,12 @@ extern "C" int sivo_debug_words(uint32_t out[64], int reset) {
     });
 }
 #endif
+
+// Test: LocalBundleAdjustment with other iteration budgets than the product's (5, 10) — the product's own function (ba_solve.hip).
+extern "C" int sivo_debug_local_ba_budget(double *poses, const uint8_t *pose_fixed, int n_poses, double *points, int n_points,
+                                          const SivoEdge *edges, int64_t n_edges, const double intr[5], const volatile uint8_t *stop_flag,
+                                          uint8_t *outlier, int cov_pose, double *cov, int *cov_ok, int *iterations, int *trials,
+                                          int it_first, int it_second, const SivoBaOptions *opts) {
+    return local_ba_budget(poses, pose_fixed, n_poses, points, n_points, edges, n_edges, intr, stop_flag, outlier, cov_pose, cov, cov_ok,
+                           iterations, trials, it_first, it_second, opts);
+}

@@ -82,7 +82,11 @@ def test_local_ba_config5_matches_oracle(oracle):
     assert (g["iterations"], g["trials"]) == (o["iterations"], o["trials"])
     np.testing.assert_allclose(g["poses"], o["poses"], atol=1e-9, rtol=0)
     np.testing.assert_allclose(g["points"], o["points"], atol=1e-7, rtol=0)
-    assert (g["outlier"] != o["outlier"]).sum() <= 2            # chi2 within 1e-9 of 5.991 / 7.815 may flip
+    # device and oracle err agree to 1e-8 (test_ba_optimize_matches_oracle): < 6e-8 in chi2 at the thresholds, so only an edge whose
+    # chi2 lies within 1e-6 of 5.991 / 7.815 may flip, and every observation the first classification excluded is reported
+    decided = np.abs(o["chi2"] - np.where(edges["stereo"] != 0, 7.815, 5.991)) > 1e-6
+    assert np.array_equal(g["outlier"][decided], o["outlier"][decided])
+    assert g["outlier"][o["level"] != 0].all()
     assert g["cov_ok"] and o["cov_ok"]
     np.testing.assert_allclose(g["cov"], o["cov"], rtol=1e-7, atol=1e-16)
     assert np.abs(g["poses"] - poses).max() < np.abs(P0 - poses).max()
