@@ -305,7 +305,14 @@ int sivo_orb_set_gaussian(sivo_orb_t h, int variant);
  * launches), 2 GaussianBlur + the reflect-101 borders, 3 IC_Angle + computeOrbDescriptor (one wave per keypoint).  Default 15: four launches
  * and NO copy per image (the kernels read the kept keys from, and write candidates and [angle | descriptor] records to, pinned host memory);
  * 0 = the fifteen launches of rounds 1 - 5.  Inside a frame whose network keeps every CU busy 14 is 0.6 % faster than 15 (the level-by-level
- * resize kernels need no LDS); results are bit-identical in every mode (tests/test_gpu_orb.py). */
+ * resize kernels need no LDS); results are bit-identical in every mode (tests/test_gpu_orb.py).
+ * Bit 4 (value 16): the quadtree on the device.  After the FAST group (either form) one kernel distributes the candidates of every level,
+ * one workgroup per level, reading candidates and offsets where FAST wrote them; the blur group and the angle / descriptor group follow, the
+ * latter over fixed per-level slot ranges of max(features_per_level + 3, 4 * n_ini) keys whose waves past a level's count exit.  The host
+ * waits ONCE, at the end, and reads the per-level counts, the kept words and the records; keys and descriptors are bit-identical to modes
+ * 0 - 15 (tests/test_gpu_orb_quadtree.py).  An extractor whose nfeatures gives a level more than 2048 cells is refused
+ * (SIVO_ERR_INVALID_ARGUMENT, the mode unchanged); a status word of the kernel -> SIVO_ERR_RUNTIME after both streams are drained.  The
+ * default stays 15.  The call takes the handle's lock: it waits for a running extraction. */
 int sivo_orb_set_launch_mode(sivo_orb_t h, int mode);
 /* GetScaleFactors / GetInverseScaleFactors / GetScaleSigmaSquares /
  * GetInverseScaleSigmaSquares + mnFeaturesPerLevel; arrays of nlevels. */
@@ -343,6 +350,19 @@ int sivo_orb_candidates(sivo_orb_t h, int level, SivoKeyPoint *out, int capacity
 /* DistributeOctTree (ORBextractor.cc:544-750), host only (sequential list surgery). */
 int sivo_orb_distribute(const SivoKeyPoint *keys, int n, int min_x, int max_x, int min_y, int max_y,
                         int n_features, SivoKeyPoint *out, int capacity, int *n_out);
+/* DistributeOctTree of n_sets candidate sets in one launch, one workgroup each; results equal sivo_orb_distribute on each set byte for byte.
+ * Arrays are host arrays; set s is keys[set_off[s] .. set_off[s + 1]) in the region [min_x[s], max_x[s]) x [min_y[s], max_y[s]), its kept keys
+ * are out[out_off[s] .. out_off[s + 1]).  A key must be what FAST produces (and what the kernel's packed word x:12 | y:12 | response:8
+ * holds): integer-valued x in [0, max_x - min_x) and y in [0, max_y - min_y), both extents <= 4096, integer-valued response in [0, 256); the
+ * other fields of a kept key are copied from its input key.  Refused with SIVO_ERR_INVALID_ARGUMENT and a message before any device is
+ * touched: any other key, an empty region, round(W / H) < 1, n_features < 1, offsets that do not start at 0 or that decrease, NULL with a
+ * non-zero count.  SIVO_ERR_CAPACITY: a set whose cell bound max(n_features + 3, 4 * n_ini) exceeds the kernel's table of 2048 cells
+ * (before any device is touched), or more kept keys than out_capacity (out_off is still written).  Zero sets, or only empty sets, launch
+ * nothing.  (How the rounds of the reference's loop become data-parallel steps: sivo_amd/csrc/orb_quadtree_math.hpp) */
+int sivo_orb_distribute_batch_dev(int n_sets, const int64_t *set_off /* n_sets + 1 */, const SivoKeyPoint *keys,
+                                  const int32_t *min_x, const int32_t *max_x, const int32_t *min_y, const int32_t *max_y,
+                                  const int32_t *n_features, int64_t out_capacity, SivoKeyPoint *out,
+                                  int64_t *out_off /* n_sets + 1 */, int device);
 
 /* ===========================================================================
  * Hamming matching — stands behind SIVO::ORBmatcher

@@ -184,6 +184,7 @@ SIGNATURES = {
     "sivo_orb_level": [_vp, _i, _vp, _sz, _pi32, _pi32],
     "sivo_orb_candidates": [_vp, _i, _vp, _i, _pi32],
     "sivo_orb_distribute": [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _pi32],
+    "sivo_orb_distribute_batch_dev": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _i],
     "sivo_hamming_matrix_dev": [_vp, _i, _vp, _i, _vp, _vp],
     "sivo_hamming_matrix": [_vp, _i, _vp, _i, _vp],
     "sivo_hamming_argmin2_dev": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -44,6 +44,12 @@ ORBextractor::~ORBextractor() {
     if (mpHandle) sivo_orb_destroy(mpHandle);
 }
 
+void ORBextractor::SetLaunchMode(int mode) {
+    const int rc = sivo_orb_set_launch_mode(mpHandle, mode);
+    if (rc == SIVO_ERR_INVALID_ARGUMENT) throw std::invalid_argument(std::string("ORBextractor::SetLaunchMode: ") + sivo_last_error());
+    if (rc != SIVO_OK) throw std::runtime_error(std::string("ORBextractor::SetLaunchMode: ") + sivo_last_error());
+}
+
 void ORBextractor::operator()(cv::InputArray _image, cv::InputArray /*_mask*/, std::vector<cv::KeyPoint> &_keypoints,
                               cv::OutputArray _descriptors) {
     if (_image.empty()) return;                       // :1023-1024

@@ -45,6 +45,11 @@ class ORBextractor {
 
     sivo_orb *handle() { return mpHandle; }   // for the device-side stereo matcher
 
+    // How an extraction is issued (sivo_orb_set_launch_mode): bits 0 - 3 one launch per kernel group, bit 4 the quadtree keypoint
+    // distribution on the device (31 = all of it, one host wait per image); the library's default is 15.  Same keys and descriptors in
+    // every mode.  Throws std::invalid_argument for a mode the extractor cannot take (bit 4 with more than 2045 features on a level).
+    void SetLaunchMode(int mode);
+
     // Which OpenCV's GaussianBlur 8U taps new extractors blur the descriptor image with (sivo_orb_set_gaussian: 0 = OpenCV 3.2 - 3.4.12 /
     // 4.0 - 4.5.0, 1 = OpenCV >= 3.4.13 / >= 4.5.1).  Initialised from the OpenCV version this file is compiled against.
     static int sGaussianVariant;

@@ -22,6 +22,9 @@
 //                        (every workgroup adds up the published counts of the cells before it) and the ordered emission
 //   -> ONE D2H (cell offsets + candidates) -> host quadtree (orb_host.cpp) -> H2D kept keypoints ->
 //   orient_describe_kernel  IC angle + rBRIEF of a keypoint in one wave -> ONE D2H (angle | descriptor records).
+// Launch mode bit 4 (sivo_orb_set_launch_mode): the quadtree on the device too (orb_quadtree.hip, one workgroup per level) —
+//   fast_cells_kernel -> orb_quadtree_kernel -> blur_border_kernel -> orient_describe_slots_kernel -> ONE wait; the host reads counts,
+//   kept words and records from pinned memory.
 // Geometries whose pyramid footprint does not fit the staging buffers (more levels / larger scale steps than ORB-SLAM uses) take the
 // level-by-level launches (copy_level0_kernel + resize_kernel).
 #include <hip/hip_runtime.h>
@@ -35,10 +38,12 @@
 #include <future>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "common.hpp"
 #include "orb.hpp"
+#include "orb_quadtree.hpp"
 
 namespace sivo {
 
@@ -454,11 +459,8 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
 // reduction is exact.  Descriptor, on the blurred level image: lane l evaluates tests 4l..4l+3 (a nibble); lanes pair up into
 // bytes.  Result record per keypoint: [angle f32 | 32 descriptor bytes] — one D2H copy for both.
 constexpr int KP_REC = 36;
-__global__ __launch_bounds__(256) void orient_describe_kernel(const uint8_t *pyr, const uint8_t *blur, LevelTable T, const DevKp *kps,
-                                                             int n, uint8_t *rec) {
-    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (k >= n) return;
-    const DevKp kp = kps[k];
+__device__ __forceinline__ void orient_describe_body(const uint8_t *pyr, const uint8_t *blur, const LevelTable &T, const DevKp kp, int k, int lane,
+                                                     uint8_t *rec) {
     const LevelInfo L = T.lv[kp.level];
     const int kx = __float2int_rn(kp.x), ky = __float2int_rn(kp.y);
     float deg;
@@ -501,6 +503,34 @@ __global__ __launch_bounds__(256) void orient_describe_kernel(const uint8_t *pyr
     const uint32_t byte = (uint32_t)(nib | (hi << 4)) & 0xffu;                // (valid on even lanes: byte lane / 2 of the descriptor)
     const uint32_t w = byte | (__shfl_down(byte, 2) << 8) | (__shfl_down(byte, 4) << 16) | (__shfl_down(byte, 6) << 24);
     if ((lane & 7) == 0) reinterpret_cast<uint32_t *>(r + 4)[lane >> 3] = w;
+}
+__global__ __launch_bounds__(256) void orient_describe_kernel(const uint8_t *pyr, const uint8_t *blur, LevelTable T, const DevKp *kps,
+                                                             int n, uint8_t *rec) {
+    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= n) return;
+    orient_describe_body(pyr, blur, T, kps[k], k, lane, rec);
+}
+
+// ---- launch mode bit 4: the kept keys come from the device quadtree (orb_quadtree.hip), not from the host.  Level l owns the fixed slot
+// range [base[l], base[l + 1]) of max(features_per_level + 3, 4 * n_ini) keys; the quadtree kernel left counts[l] packed words
+// (x:12 | y:12 | response:8, relative to the 16-px border) at the start of it.  One wave per slot as above; the waves past a level's
+// count exit.  Results are indexed by slot.
+struct SlotTable { int n; int base[MAX_LEVELS + 1]; };
+__device__ __forceinline__ bool slot_key(const SlotTable &S, const int32_t *counts, const uint32_t *kept, int k, DevKp *kp) {
+    if (k >= S.base[S.n]) return false;
+    int l = 0;
+    while (l + 1 < S.n && k >= S.base[l + 1]) ++l;
+    if (k - S.base[l] >= counts[l]) return false;
+    const uint32_t w = kept[k];
+    kp->x = (float)((int)(w & 0xfff) + EDGE_THRESHOLD - 3); kp->y = (float)((int)((w >> 12) & 0xfff) + EDGE_THRESHOLD - 3); kp->level = l;
+    return true;
+}
+__global__ __launch_bounds__(256) void orient_describe_slots_kernel(const uint8_t *pyr, const uint8_t *blur, LevelTable T, SlotTable S,
+                                                                   const int32_t *counts, const uint32_t *kept, uint8_t *rec) {
+    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    DevKp kp;
+    if (!slot_key(S, counts, kept, k, &kp)) return;
+    orient_describe_body(pyr, blur, T, kp, k, lane, rec);
 }
 
 // ---- the separate forms (launch mode bits 2 / 3 clear): A/B against the merged kernels above
@@ -553,11 +583,7 @@ __global__ __launch_bounds__(256) void blur_kernel(const uint8_t *pyr, uint8_t *
 
 // IC_Angle (ORBextractor.cc:75-100): one wave per keypoint, lane = patch row v in [-15,15];
 // integer moments are order independent, so the wave reduction is exact.
-__global__ __launch_bounds__(256) void angle_kernel(const uint8_t *pyr, LevelTable T, const DevKp *kps, int n,
-                                                   float *angles) {
-    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (k >= n) return;
-    const DevKp kp = kps[k];
+__device__ __forceinline__ void angle_body(const uint8_t *pyr, const LevelTable &T, const DevKp kp, int k, int lane, float *angles) {
     const LevelInfo L = T.lv[kp.level];
     const uint8_t *center = pyr + L.off + (int64_t)(EDGE_THRESHOLD + __float2int_rn(kp.y)) * L.step + EDGE_THRESHOLD +
                             __float2int_rn(kp.x);
@@ -574,14 +600,24 @@ __global__ __launch_bounds__(256) void angle_kernel(const uint8_t *pyr, LevelTab
     for (int o = 32; o >= 1; o >>= 1) { m10 += __shfl_xor(m10, o); m01 += __shfl_xor(m01, o); }
     if (lane == 0) angles[k] = fast_atan2_deg((float)m01, (float)m10);
 }
+__global__ __launch_bounds__(256) void angle_kernel(const uint8_t *pyr, LevelTable T, const DevKp *kps, int n,
+                                                   float *angles) {
+    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= n) return;
+    angle_body(pyr, T, kps[k], k, lane, angles);
+}
+__global__ __launch_bounds__(256) void angle_slots_kernel(const uint8_t *pyr, LevelTable T, SlotTable S, const int32_t *counts,
+                                                         const uint32_t *kept, float *angles) {
+    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    DevKp kp;
+    if (!slot_key(S, counts, kept, k, &kp)) return;
+    angle_body(pyr, T, kp, k, lane, angles);
+}
 
 // computeOrbDescriptor (ORBextractor.cc:104-150) on the blurred level image: one wave per
 // keypoint, lane l evaluates tests 4l..4l+3 (a nibble); lanes pair up into bytes.
-__global__ __launch_bounds__(256) void descriptor_kernel(const uint8_t *blur, LevelTable T, const DevKp *kps,
-                                                        const float *angles, int n, uint8_t *desc) {
-    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (k >= n) return;
-    const DevKp kp = kps[k];
+__device__ __forceinline__ void descriptor_body(const uint8_t *blur, const LevelTable &T, const DevKp kp, const float *angles, int k, int lane,
+                                                uint8_t *desc) {
     const LevelInfo L = T.lv[kp.level];
     const float factorPI = (float)(3.141592653589793238462643383279502884 / 180.f);
     const float angle = __fmul_rn(angles[k], factorPI);
@@ -602,6 +638,19 @@ __global__ __launch_bounds__(256) void descriptor_kernel(const uint8_t *blur, Le
     }
     const int hi = __shfl_down(nib, 1);
     if ((lane & 1) == 0) desc[(int64_t)k * 32 + (lane >> 1)] = (uint8_t)(nib | (hi << 4));
+}
+__global__ __launch_bounds__(256) void descriptor_kernel(const uint8_t *blur, LevelTable T, const DevKp *kps,
+                                                        const float *angles, int n, uint8_t *desc) {
+    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= n) return;
+    descriptor_body(blur, T, kps[k], angles, k, lane, desc);
+}
+__global__ __launch_bounds__(256) void descriptor_slots_kernel(const uint8_t *blur, LevelTable T, SlotTable S, const int32_t *counts,
+                                                              const uint32_t *kept, const float *angles, uint8_t *desc) {
+    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    DevKp kp;
+    if (!slot_key(S, counts, kept, k, &kp)) return;
+    descriptor_body(blur, T, kp, angles, k, lane, desc);
 }
 
 // ---------------------------------------------------------------- stereo SAD (Frame.cc:543-583)
@@ -691,7 +740,15 @@ struct sivo_orb {
     // network keeps every CU busy; 8 runs each on one box, profiles/r06_orb_launch_modes.log): 15 -> 144.2 frames/s, 14 (pyramid level
     // by level: its resize kernels need no LDS and slip in beside the network's whole-LDS workgroups) -> 145.1, 0 (the round-5 kernels) ->
     // 146 / 145; round 5's code with its 12 copies per stereo pair -> 143.8.  Alone on the GPU 15 is the fastest (1.0 ms per stereo pair).
+    // Bit 4 (16): the quadtree on the device too — one kernel between FAST and the angle / descriptor group, the host waits once.
     int launch_mode = 15;
+    // launch mode bit 4: one candidate set per level (orb_quadtree.hip); the kept words of level l go to the slots [base[l], base[l + 1])
+    QtSet qt_sets[MAX_LEVELS];
+    QtSet *d_qt_sets = nullptr;
+    SlotTable qt_slots{};
+    int32_t *h_qt = nullptr, *d_qt = nullptr;       // pinned: [count per level | status per level | kept words per slot]; d_qt = its device address
+    uint32_t *d_qt_words = nullptr;                 // the kernel's scratch: a copy of the candidates and a list position each
+    uint16_t *d_qt_ids = nullptr;
     uint32_t *d_slots = nullptr;    // three-launch FAST: ncells x cap candidate slots
     int *d_counts = nullptr, *d_offsets = nullptr;
     PyrTables pyr_tabs{};
@@ -738,7 +795,8 @@ struct sivo_orb {
     }
 
     void free_geometry() {
-        for (void *p : {(void *)d_pyr, (void *)d_blur, (void *)d_src, (void *)d_cells, (void *)d_status, (void *)d_tiles, (void *)d_slots, (void *)d_counts, (void *)d_offsets})
+        for (void *p : {(void *)d_pyr, (void *)d_blur, (void *)d_src, (void *)d_cells, (void *)d_status, (void *)d_tiles, (void *)d_slots, (void *)d_counts, (void *)d_offsets,
+                        (void *)d_qt_sets, (void *)d_qt_words, (void *)d_qt_ids})
             if (p) (void)hipFree(p);
         for (int l = 0; l < MAX_LEVELS; ++l) {
             if (d_xt[l]) (void)hipFree(d_xt[l]);
@@ -746,6 +804,8 @@ struct sivo_orb {
             d_xt[l] = nullptr; d_yt[l] = nullptr;
         }
         if (h_fast) (void)hipHostFree(h_fast);
+        if (h_qt) (void)hipHostFree(h_qt);
+        h_qt = d_qt = nullptr; d_qt_sets = nullptr; d_qt_words = nullptr; d_qt_ids = nullptr;
         d_pyr = d_blur = d_src = nullptr; d_cells = nullptr; d_fast = nullptr; h_fast = nullptr;
         d_status = nullptr; d_err = nullptr; d_tiles = nullptr; d_slots = nullptr; d_counts = nullptr; d_offsets = nullptr; ntiles = 0; fused_pyramid = false;
         src_bytes = 0;
@@ -951,6 +1011,28 @@ void setup_geometry(sivo_orb &o, int rows, int cols) {
     o.d_offsets = dev_alloc<int>(nc + 1);
     o.d_err = o.d_fast + nc + 1;                    // (inside the region the host copies: zero from the memset above)
     SIVO_HIP(hipMemset(o.d_status, 0, (nc + 1) * sizeof(uint32_t)));
+    // the device quadtree's sets (launch mode bit 4): level l distributes the candidates of its cells over the region the reference hands
+    // DistributeOctTree (ORBextractor.cc:821-822), and keeps at most max(features_per_level + 3, 4 * n_ini) of them
+    o.qt_slots.n = o.nlevels;
+    o.qt_slots.base[0] = 0;
+    for (int l = 0; l < o.nlevels; ++l) {
+        QtSet &q = o.qt_sets[l];
+        q.off_b = o.level_cell_begin[l]; q.off_e = o.level_cell_begin[l + 1];
+        q.w = o.table.lv[l].cols - 2 * (EDGE_THRESHOLD - 3); q.h = o.table.lv[l].rows - 2 * (EDGE_THRESHOLD - 3);
+        quadtree_roots(q.w, q.h, &q.n_ini, &q.h_x);
+        q.target = o.feat_per_level[l];
+        q.slot_base = o.qt_slots.base[l];
+        q.slot_count = (int)std::min<int64_t>(qt_cell_bound(q.target, q.n_ini), QT_MAX_CELLS);
+        o.qt_slots.base[l + 1] = q.slot_base + q.slot_count;
+    }
+    o.d_qt_sets = dev_alloc<QtSet>(o.nlevels);
+    SIVO_HIP(hipMemcpy(o.d_qt_sets, o.qt_sets, o.nlevels * sizeof(QtSet), hipMemcpyHostToDevice));
+    o.d_qt_words = dev_alloc<uint32_t>(o.dense_cap);
+    o.d_qt_ids = dev_alloc<uint16_t>(o.dense_cap);
+    const size_t qt_words = 2 * (size_t)MAX_LEVELS + (size_t)o.qt_slots.base[o.nlevels];
+    SIVO_HIP(hipHostMalloc((void **)&o.h_qt, qt_words * sizeof(int32_t), ORB_PINNED));
+    std::memset(o.h_qt, 0, qt_words * sizeof(int32_t));
+    SIVO_HIP(hipHostGetDevicePointer((void **)&o.d_qt, o.h_qt, 0));
     o.epoch = 0;
     o.have_pyramid = false;
 }
@@ -978,6 +1060,7 @@ int extract_locked(sivo_orb &o, const uint8_t *d_src, int rows, int cols, int st
         SIVO_HIP(hipStreamWaitEvent(st, o.ev_pyr, 0));
     }
     const LevelTable &T = o.table;
+    if (o.launch_mode & 16) ensure_kp_capacity(o, o.qt_slots.base[o.nlevels]);      // (records are indexed by slot)
     auto mark = [&](int k, bool end, hipStream_t on) {
         if (!o.prof) return;
         if (!o.pe0[k]) { SIVO_HIP(hipEventCreate(&o.pe0[k])); SIVO_HIP(hipEventCreate(&o.pe1[k])); }
@@ -1003,8 +1086,9 @@ int extract_locked(sivo_orb &o, const uint8_t *d_src, int rows, int cols, int st
     mark(0, true, st);
     SIVO_HIP(hipEventRecord(o.ev_pyr, st));
     // ---- blur + borders on the second stream (they need interiors only), overlapping FAST + the host quadtree
-    SIVO_HIP(hipStreamWaitEvent(o.stream2, o.ev_pyr, 0));
-    {
+    // (launch mode bit 4: issued after the quadtree kernel instead)
+    auto launch_blur = [&] {
+        SIVO_HIP(hipStreamWaitEvent(o.stream2, o.ev_pyr, 0));
         int max_tiles = BORDER_BLOCKS;
         for (int l = 0; l < o.nlevels; ++l) max_tiles = std::max(max_tiles, cdiv(T.lv[l].cols, 32) * cdiv(T.lv[l].rows, 32));
         mark(1, false, o.stream2);
@@ -1017,9 +1101,11 @@ int extract_locked(sivo_orb &o, const uint8_t *d_src, int rows, int cols, int st
         }
         mark(1, true, o.stream2);
         SIVO_HIP(hipEventRecord(o.ev_blur, o.stream2));
-    }
-    // ---- FAST cells -> ordered candidate list, written by the kernels into the host's (pinned) memory: [cell offsets | candidates]
+    };
     const int nc = (int)o.cells.size();
+    const bool device_quadtree = (o.launch_mode & 16) && nc > 0;
+    if (!device_quadtree) launch_blur();
+    // ---- FAST cells -> ordered candidate list, written by the kernels into the host's (pinned) memory: [cell offsets | candidates]
     int total = 0;
     int *h_off = o.h_fast;
     const uint32_t *h_dense = reinterpret_cast<const uint32_t *>(o.h_fast + o.off_words);
@@ -1036,7 +1122,35 @@ int extract_locked(sivo_orb &o, const uint8_t *d_src, int rows, int cols, int st
             hipLaunchKernelGGL(compact_kernel, dim3(nc), dim3(64), 0, st, o.d_slots, o.cap, o.d_counts, o.d_offsets, reinterpret_cast<uint32_t *>(o.d_fast + o.off_words));
         }
         mark(2, true, st);
+        if (device_quadtree) {
+            // ---- quadtree kernel over all levels, blur group, angle / descriptor group over the slot ranges: ONE wait, at the end
+            const int slots = o.qt_slots.base[o.nlevels];
+            int32_t *h_count = o.h_qt, *h_status = o.h_qt + MAX_LEVELS;
+            int32_t *d_count = o.d_qt, *d_qstatus = o.d_qt + MAX_LEVELS;
+            const uint32_t *d_kept = reinterpret_cast<const uint32_t *>(o.d_qt + 2 * MAX_LEVELS);
+            for (int l = 0; l < o.nlevels; ++l) { h_count[l] = 0; h_status[l] = -1; }
+            quadtree_launch(st, o.nlevels, o.d_qt_sets, o.d_fast, (int32_t)o.dense_cap, reinterpret_cast<const uint32_t *>(o.d_fast + o.off_words),
+                            o.d_qt_words, o.d_qt_ids, reinterpret_cast<uint32_t *>(o.d_qt + 2 * MAX_LEVELS), nullptr, d_count, d_qstatus);
+            launch_blur();
+            if (o.launch_mode & 8) {
+                SIVO_HIP(hipStreamWaitEvent(st, o.ev_blur, 0));
+                mark(3, false, st);
+                hipLaunchKernelGGL(orient_describe_slots_kernel, dim3(cdiv(slots, 4)), dim3(256), 0, st, o.d_pyr, o.d_blur, T, o.qt_slots, d_count, d_kept, o.d_rec);
+                mark(3, true, st);
+            } else {
+                mark(3, false, st);
+                hipLaunchKernelGGL(angle_slots_kernel, dim3(cdiv(slots, 4)), dim3(256), 0, st, o.d_pyr, T, o.qt_slots, d_count, d_kept, o.d_angles);
+                mark(3, true, st);
+                SIVO_HIP(hipStreamWaitEvent(st, o.ev_blur, 0));
+                mark(4, false, st);
+                hipLaunchKernelGGL(descriptor_slots_kernel, dim3(cdiv(slots, 4)), dim3(256), 0, st, o.d_blur, T, o.qt_slots, d_count, d_kept, o.d_angles, o.d_desc);
+                mark(4, true, st);
+                SIVO_HIP(hipMemcpyAsync(o.h_rec, o.d_angles, (size_t)slots * 4, hipMemcpyDeviceToHost, st));
+                SIVO_HIP(hipMemcpyAsync(o.h_rec + (size_t)o.kp_cap * 4, o.d_desc, (size_t)slots * 32, hipMemcpyDeviceToHost, st));
+            }
+        }
         SIVO_HIP(hipStreamSynchronize(st));                 // the kernels wrote offsets and candidates into h_fast themselves
+        if (device_quadtree) SIVO_HIP(hipStreamSynchronize(o.stream2));     // (drained before any error below is reported)
         total = h_off[nc];
         if (total < 0 || (size_t)total > o.dense_cap || h_off[nc + 1] != 0)
             return fail(SIVO_ERR_RUNTIME, "FAST candidate scan did not complete (total %d, error word %d)", total, h_off[nc + 1]);
@@ -1045,7 +1159,13 @@ int extract_locked(sivo_orb &o, const uint8_t *d_src, int rows, int cols, int st
     // ---- host: quadtree per level (ORBextractor.cc:821-841)
     o.last_candidates.assign(o.nlevels, {});
     std::vector<SivoKeyPoint> kept, all;
-    std::vector<int> level_count(o.nlevels, 0);
+    std::vector<int> level_count(o.nlevels, 0), rec_of;     // rec_of: launch mode bit 4, the slot (= record) of every kept key
+    if (device_quadtree)
+        for (int l = 0; l < o.nlevels; ++l) {
+            const int status = o.h_qt[MAX_LEVELS + l], cnt = o.h_qt[l];
+            if (status != QT_OK || cnt < 0 || cnt > o.qt_sets[l].slot_count)
+                return fail(SIVO_ERR_RUNTIME, "device quadtree, level %d: %s (status %d, count %d)", l, quadtree_status_text(status), status, cnt);
+        }
     for (int l = 0; l < o.nlevels; ++l) {
         const int c0 = o.level_cell_begin[l], c1 = o.level_cell_begin[l + 1];
         if (c0 == c1) continue;
@@ -1070,8 +1190,19 @@ int extract_locked(sivo_orb &o, const uint8_t *d_src, int rows, int cols, int st
         if (cand.empty()) continue;
         const LevelInfo &L = T.lv[l];
         const int minB = EDGE_THRESHOLD - 3;
-        distribute_quadtree(cand.data(), (int)cand.size(), minB, L.cols - EDGE_THRESHOLD + 3, minB, L.rows - EDGE_THRESHOLD + 3,
-                            o.feat_per_level[l], kept);
+        if (device_quadtree) {      // the list the kernel left: packed words in list order
+            const uint32_t *words = reinterpret_cast<const uint32_t *>(o.h_qt + 2 * MAX_LEVELS) + o.qt_sets[l].slot_base;
+            kept.resize((size_t)o.h_qt[l]);
+            for (size_t j = 0; j < kept.size(); ++j) {
+                const uint32_t w = words[j];
+                SivoKeyPoint &k = kept[j];
+                k.x = (float)(w & 0xfff); k.y = (float)((w >> 12) & 0xfff);
+                k.size = 7.f; k.angle = -1.f; k.response = (float)(w >> 24); k.octave = 0; k.class_id = -1;
+                rec_of.push_back(o.qt_sets[l].slot_base + (int)j);
+            }
+        } else
+            distribute_quadtree(cand.data(), (int)cand.size(), minB, L.cols - EDGE_THRESHOLD + 3, minB, L.rows - EDGE_THRESHOLD + 3,
+                                o.feat_per_level[l], kept);
         const int scaled_patch = (int)(PATCH_SIZE * o.scale[l]);
         for (SivoKeyPoint &k : kept) {
             k.x += minB; k.y += minB; k.octave = l; k.size = (float)scaled_patch;
@@ -1083,16 +1214,19 @@ int extract_locked(sivo_orb &o, const uint8_t *d_src, int rows, int cols, int st
     *n_out = n;
     if (n == 0) { SIVO_HIP(hipStreamSynchronize(o.stream2)); return SIVO_OK; }
     if (n > capacity) { SIVO_HIP(hipStreamSynchronize(o.stream2)); return fail(SIVO_ERR_CAPACITY, "%d keypoints, capacity %d", n, capacity); }
-    // ---- device: orientation + descriptors
-    ensure_kp_capacity(o, n);
-    for (int i = 0; i < n; ++i) o.h_kps[i] = DevKp{all[i].x, all[i].y, all[i].octave};
-    if (o.launch_mode & 8) {
+    // ---- device: orientation + descriptors (launch mode bit 4: done already, over the slots)
+    if (device_quadtree) {
+    } else if (o.launch_mode & 8) {
+        ensure_kp_capacity(o, n);
+        for (int i = 0; i < n; ++i) o.h_kps[i] = DevKp{all[i].x, all[i].y, all[i].octave};
         SIVO_HIP(hipStreamWaitEvent(st, o.ev_blur, 0));
         mark(3, false, st);
         hipLaunchKernelGGL(orient_describe_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, o.d_pyr, o.d_blur, T, o.d_kps, n, o.d_rec);
         mark(3, true, st);
         SIVO_HIP(hipStreamSynchronize(st));
     } else {
+        ensure_kp_capacity(o, n);
+        for (int i = 0; i < n; ++i) o.h_kps[i] = DevKp{all[i].x, all[i].y, all[i].octave};
         mark(3, false, st);
         hipLaunchKernelGGL(angle_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, o.d_pyr, T, o.d_kps, n, o.d_angles);
         mark(3, true, st);
@@ -1120,15 +1254,16 @@ int extract_locked(sivo_orb &o, const uint8_t *d_src, int rows, int cols, int st
         ++o.prof_calls; o.prof_keys += n;
     }
     // ---- assemble (ORBextractor.cc:1068-1081): pt *= scale for level > 0
+    auto rec = [&](int i) { return (size_t)(device_quadtree ? rec_of[i] : i); };
     for (int i = 0; i < n; ++i) {
         SivoKeyPoint k = all[i];
-        std::memcpy(&k.angle, recs ? o.h_rec + (size_t)i * KP_REC : o.h_rec + (size_t)i * 4, 4);
+        std::memcpy(&k.angle, recs ? o.h_rec + rec(i) * KP_REC : o.h_rec + rec(i) * 4, 4);
         if (k.octave != 0) { const float s = o.scale[k.octave]; k.x *= s; k.y *= s; }
         keypoints[i] = k;
     }
     if (descriptors)
         for (int i = 0; i < n; ++i)
-            std::memcpy(descriptors + (size_t)i * 32, recs ? o.h_rec + (size_t)i * KP_REC + 4 : o.h_rec + (size_t)o.kp_cap * 4 + (size_t)i * 32, 32);
+            std::memcpy(descriptors + (size_t)i * 32, recs ? o.h_rec + rec(i) * KP_REC + 4 : o.h_rec + (size_t)o.kp_cap * 4 + rec(i) * 32, 32);
     return SIVO_OK;
 }
 
@@ -1142,7 +1277,14 @@ int extract_locked(sivo_orb &o, const uint8_t *d_src, int rows, int cols, int st
 extern "C" int sivo_orb_set_launch_mode(sivo_orb_t h, int mode) {
     return guarded([&] {
         if (!h) throw std::invalid_argument("null handle");
-        if (mode < 0 || mode > 15) throw std::invalid_argument("launch mode: bits 0 - 3 (pyramid, FAST, blur + borders, angle + descriptor in one launch each)");
+        if (mode < 0 || mode > 31)
+            throw std::invalid_argument("launch mode: bits 0 - 3 (pyramid, FAST, blur + borders, angle + descriptor in one launch each), bit 4 (the quadtree on the device)");
+        std::lock_guard<std::mutex> not_during_an_extraction(h->mu);
+        if (mode & 16)
+            for (int l = 0; l < h->nlevels; ++l)
+                if (h->feat_per_level[l] + 3 > QT_MAX_CELLS)
+                    throw std::invalid_argument("launch mode bit 4: level " + std::to_string(l) + " asks for " + std::to_string(h->feat_per_level[l]) +
+                                                " features, the device quadtree's table holds " + std::to_string(QT_MAX_CELLS) + " cells (features + 3)");
         h->launch_mode = mode;
         return SIVO_OK;
     });

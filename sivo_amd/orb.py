@@ -22,7 +22,8 @@ class ORBextractor:
     def __init__(self, nfeatures=2000, scale_factor=1.2, nlevels=8, ini_th_fast=20, min_th_fast=7, device=0, gaussian="rounded", launch_mode=None):
         """gaussian: the OpenCV GaussianBlur 8U taps the reference build was linked with (sivo_orb_set_gaussian): "rounded" =
         OpenCV 3.2 - 3.4.12 / 4.0 - 4.5.0 (default), "ed" = OpenCV >= 3.4.13 / >= 4.5.1.  launch_mode (sivo_orb_set_launch_mode): bits 0 - 3 = the pyramid /
-        FAST + scan + emission / blur + borders / angle + descriptor in one launch each; None = the library's default (15: four launches per image)."""
+        FAST + scan + emission / blur + borders / angle + descriptor in one launch each, bit 4 (16) = the quadtree keypoint distribution on the
+        device too (one host wait per image; 31 = all of it); None = the library's default (15: four launches per image, the quadtree on the host)."""
         h = C.c_void_p()
         self._L = lib()          # the library this object lives in (product, or the diagnostic build inside `with _lib.use("diag")`)
         check(self._L.sivo_orb_create(nfeatures, C.c_float(scale_factor), nlevels, ini_th_fast, min_th_fast, device, C.byref(h)))
@@ -108,6 +109,28 @@ def distribute_octtree(keys, min_x, max_x, min_y, max_y, n_features):
     n = C.c_int32(0)
     check(lib().sivo_orb_distribute(_p(keys), len(keys), min_x, max_x, min_y, max_y, n_features, _p(out), len(out), C.byref(n)))
     return out[:n.value].copy()
+
+
+def distribute_octtree_batch_dev(sets, min_x, max_x, min_y, max_y, n_features, device=0):
+    """DistributeOctTree of every key set of `sets` on the device in one launch, one workgroup per set (sivo_orb_distribute_batch_dev);
+    min_x ... n_features: one value per set.  A list of kept-key arrays, each equal to distribute_octtree on its set byte for byte.  Keys
+    must be what FAST produces: integer x, y inside the region (relative to its corner), integer response in [0, 256)."""
+    sets = [np.ascontiguousarray(s, KP_DTYPE) for s in sets]
+    n = len(sets)
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum([len(s) for s in sets])
+    keys = np.concatenate(sets) if n else np.zeros(0, KP_DTYPE)
+    cols = [np.ascontiguousarray(c, np.int32) for c in (min_x, max_x, min_y, max_y, n_features)]
+    assert all(c.shape == (n,) for c in cols), "one region and one n_features per set"
+    out = np.zeros(max(len(keys), 1), KP_DTYPE)              # (a list never holds more cells than candidates)
+    out_off = np.zeros(n + 1, np.int64)
+    check(lib().sivo_orb_distribute_batch_dev(n, _p(off), _p(keys), *[_p(c) for c in cols], len(keys), _p(out), _p(out_off), device))
+    return [out[out_off[s]:out_off[s + 1]].copy() for s in range(n)]
+
+
+def distribute_octtree_dev(keys, min_x, max_x, min_y, max_y, n_features, device=0):
+    """DistributeOctTree of one key set on the device: distribute_octtree_batch_dev with one set."""
+    return distribute_octtree_batch_dev([keys], [min_x], [max_x], [min_y], [max_y], [n_features], device)[0]
 
 
 def extract_pair(left, right, image_left, image_right):
