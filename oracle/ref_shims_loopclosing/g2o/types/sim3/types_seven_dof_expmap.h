@@ -1,0 +1,2 @@
+#pragma once
+#include "../../../g2o_sim3_standin.hpp"

@@ -14,7 +14,10 @@
 #define ORBEXTRACTOR_H
 #define ORBVOCABULARY_H
 #define KEYFRAMEDATABASE_H
+#ifndef REF_LOOPCLOSING_BUILD      // (ref_shims_loopclosing/loopclosing_standins.h: LoopClosing.h and Converter.h are the reference's there)
 #define LOOPCLOSING_H
+#define CONVERTER_H
+#endif
 #define SYSTEM_H
 #define VIEWER_H
 #define FRAMEDRAWER_H
@@ -22,7 +25,6 @@
 #define ORBMATCHER_H
 #define OPTIMIZER_H
 #define PNPSOLVER_H
-#define CONVERTER_H
 #define BAYESIAN_SEGNET_BAYESIAN_SEGNET_HPP
 #ifndef EIGEN_MAKE_ALIGNED_OPERATOR_NEW
 #define EIGEN_MAKE_ALIGNED_OPERATOR_NEW
@@ -108,14 +110,17 @@ class BayesianSegNet {};
 class ORBVocabulary {
  public:
     void transform(const std::vector<cv::Mat> &, DBoW2::BowVector &, DBoW2::FeatureVector &, int) {}
+    double score(const DBoW2::BowVector &, const DBoW2::BowVector &) const { return 0; }
 };
 class ORBextractor {
  public:
     ORBextractor(int, float, int, int, int) {}
 };
+#ifndef REF_LOOPCLOSING_BUILD
 struct Converter {
     static std::vector<cv::Mat> toDescriptorVector(const cv::Mat &) { return std::vector<cv::Mat>(); }
 };
+#endif
 
 class Frame {
  public:
@@ -171,13 +176,16 @@ class KeyFrameDatabase {
     void erase(KeyFrame *pKF) { erased.push_back(pKF); }
     void clear() {}
     std::vector<KeyFrame *> DetectRelocalizationCandidates(Frame *) { return std::vector<KeyFrame *>(); }
+    std::vector<KeyFrame *> DetectLoopCandidates(KeyFrame *, float) { return std::vector<KeyFrame *>(); }
 };
 
+#ifndef REF_LOOPCLOSING_BUILD
 class LoopClosing {
  public:
     void InsertKeyFrame(KeyFrame *) {}
     void RequestReset() {}
 };
+#endif
 class System {
  public:
     enum eSensor { MONOCULAR = 0, STEREO = 1, RGBD = 2 };
@@ -198,6 +206,7 @@ class MapDrawer {
     void SetCurrentCameraPose(const cv::Mat &) {}
 };
 
+#ifndef REF_LOOPCLOSING_BUILD
 class Optimizer {
  public:
     static void LocalBundleAdjustment(KeyFrame *, bool *, Map *) {}
@@ -215,6 +224,7 @@ class ORBmatcher {
     int SearchByBoW(KeyFrame *, Frame &, std::vector<MapPoint *> &) { return 0; }
     static int DescriptorDistance(const cv::Mat &, const cv::Mat &) { return 0; }
 };
+#endif
 
 class PnPsolver {
  public:

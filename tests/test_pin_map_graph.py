@@ -34,8 +34,9 @@ The one difference the pin found (the scene that showed it is kept: bawin.random
     before the comparison, and nothing else.
 Everything else agreed: see the counts in each test's parametrisation.
 
-Still unpinned (DESIGN.md §5): nMPs / nRedundantObservations other than through the twins, LoopClosing::CorrectLoop / SearchAndFuse,
-KeyFrame::UnprojectStereo.  Where the reference is absent the same assertions read tests/golden/map_graph_reference.npz; the tests marked
+Still unpinned (DESIGN.md §5): nMPs / nRedundantObservations other than through the twins, KeyFrame::UnprojectStereo, the candidate choice
+of ORBmatcher::Fuse inside LoopClosing::SearchAndFuse (CorrectLoop, the loop fusion, SearchAndFuse's own lines and the map update behind the
+global BA: tests/test_pin_loop_closing.py).  Where the reference is absent the same assertions read tests/golden/map_graph_reference.npz; the tests marked
 gpu read only that file and tests/."""
 import os
 
