@@ -1268,6 +1268,59 @@ int sivo_localmap_update(sivo_localmap_t map, int n_slots, const int32_t *frame_
                          int32_t *local_kf, int32_t *n_local_kf, int32_t *ref_kf, int point_capacity, int32_t *local_point,
                          int32_t *n_local_points, int32_t *counts);
 
+/* The map points' attributes, resident beside the tables (reference src/orbslam/Tracking.cc:1033-1124:
+ * what the second loop of Tracking::SearchLocalPoints and the search behind it read of every
+ * local map point).  DESIGN 3.6n.  Per point of the handle: pos = mWorldPos and normal =
+ * mNormalVector (3 floats each), min_dist / max_dist = mfMinDistance / mfMaxDistance raw, as
+ * sivo_frustum_cull takes them, desc = GetDescriptor() (32 bytes), n_obs = Observations().
+ * set_points sends n_rows rows in one upload and scatters them on the device; point_idx is
+ * strictly increasing; it may be called any number of times, the later row holds.  A row is
+ * SET once a set_points has named it.  sivo_localmap_create starts with every row unset;
+ * sivo_localmap_apply keeps every stored row (the store grows by a device copy) and leaves
+ * the appended points unset; sivo_localmap_replace unsets all rows, because the caller may
+ * have renumbered.  get_points reads rows back (for tests and an adapter's checks):
+ * is_set[i] = 1 for a set row; an unset row reads as zeros.
+ * A null handle, a negative count, a NULL array with a non-zero count, an index out of range
+ * or indices that are not strictly increasing -> SIVO_ERR_INVALID_ARGUMENT before any device
+ * is touched, the handle left as it was. */
+int sivo_localmap_set_points(sivo_localmap_t map, int n_rows, const int32_t *point_idx, const float *pos, const float *normal,
+                             const float *min_dist, const float *max_dist, const uint8_t *desc, const int32_t *n_obs);
+int sivo_localmap_get_points(sivo_localmap_t map, int n_rows, const int32_t *point_idx, float *pos, float *normal, float *min_dist,
+                             float *max_dist, uint8_t *desc, int32_t *n_obs, uint8_t *is_set);
+
+/* Tracking::UpdateLocalMap and Tracking::SearchLocalPoints in one call (reference
+ * src/orbslam/Tracking.cc:1033-1124): sivo_localmap_update with the same arguments, followed by
+ * sivo_search_local_points on F over local_point[0 .. *n_local_points) with
+ *   pos, normal, min_dist, max_dist, mp_desc, mp_obs [i] = the stored attributes of local_point[i];
+ *   skip[i] = 1 where local_point[i] is a frame_point[s] >= 0 with slot_cleared[s] == 0 (the
+ *     frame's own points, which the first loop of :1035-1049 stamps) or is listed in seen_point
+ *     (the points whose mnLastFrameSeen already equals the frame's id, such as the outliers
+ *     dropped at :626-630; may be NULL with n_seen 0); bad points never reach local_point;
+ *   occ_obs[k] = n_obs[frame_point[k]] where frame_point[k] >= 0 and the slot is not cleared,
+ *     else -1.
+ * The update's outputs are sivo_localmap_update's; status, proj_x .. level (per local point;
+ * status is required, the others may each be NULL and are written for the points in view only)
+ * and *n_to_match, *n_matches are sivo_search_local_points'; match[k] (n_slots) = the position
+ * in local_point of the point matched to keypoint k, or -1.  Every output is byte for byte
+ * that of the composed pair.  With no local point or nothing in view *n_matches = 0, as the
+ * reference skips the search (:1072).  local_point is not sent up again and no per-point
+ * host array is built: a kernel reads local_point[i] and the store on the device and writes
+ * the search engine's queries, descriptors and blocked flags there.
+ * SIVO_ERR_CAPACITY as in sivo_localmap_update; nothing of the search is written then.
+ * Beyond sivo_localmap_update's refusals, with SIVO_ERR_INVALID_ARGUMENT before any device is
+ * touched: the map and the frame on different devices, n_slots != the frame's keypoint count,
+ * frustum->nlevels outside 1 .. 16 or above the frame's, log_scale_factor <= 0, a point row
+ * of the handle that is unset (the text names their count and the first index), seen_point
+ * out of range. */
+int sivo_localmap_search_local_points(sivo_localmap_t map, sivo_mframe_t F, const SivoFrustum *frustum, int n_slots,
+                                      const int32_t *frame_point, int n_kf_premarked, const int32_t *kf_premarked,
+                                      int n_point_premarked, const int32_t *point_premarked, int n_prev,
+                                      const int32_t *prev_local_kf, int n_seen, const int32_t *seen_point, float th, float nn_ratio,
+                                      int32_t *voted, uint8_t *slot_cleared, int kf_capacity, int32_t *local_kf, int32_t *n_local_kf,
+                                      int32_t *ref_kf, int point_capacity, int32_t *local_point, int32_t *n_local_points,
+                                      int32_t *counts, uint8_t *status, float *proj_x, float *proj_y, float *proj_xr, float *view_cos,
+                                      int32_t *level, int32_t *match, int *n_to_match, int *n_matches);
+
 #define SIVO_BAWIN_SLOT_NONE (-1)      /* no slot of the keyframe holds the point (a stale observation) */
 #define SIVO_BAWIN_SLOT_AMBIGUOUS (-2) /* more than one slot does */
 

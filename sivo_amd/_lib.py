@@ -242,6 +242,10 @@ SIGNATURES = {
     "sivo_localmap_sizes": [_vp, _vp],
     "sivo_localmap_export": [_vp, _vp],
     "sivo_localmap_update": [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "sivo_localmap_set_points": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sivo_localmap_get_points": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sivo_localmap_search_local_points": [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _f, _f, _vp, _vp, _i, _vp, _vp, _vp, _i,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pi32, _pi32],
     "sivo_localmap_ba_window": [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp],
     "sivo_voc_create_from_text": [C.c_char_p, C.POINTER(_vp)],
     "sivo_voc_create": [_i, _i, _i64, _vp, _vp, _vp, _vp, C.POINTER(_vp)],

@@ -8,6 +8,10 @@
 //                                                             in place of UpdateLocalKeyFrames(); UpdateLocalPoints(); (:1092-1093)
 //     dev.BAWindow(pKF, window)                               the window of Optimizer::LocalBundleAdjustment (Optimizer.cc:496-559,
 //                                                             :651-670) from ONE sivo_localmap_ba_window, as pointers
+//     dev.KeepAttributes()                                    before Rebuild: the handle also keeps every point's position, normal,
+//                                                             distance range, descriptor and Observations() (sivo_localmap_set_points),
+//                                                             which SIVO::TrackLocalMapSearch of TrackingAdapter.h needs
+//     dev.TouchGeometry(pMP)                                  a point moved or changed its descriptor, its observations did not
 // as header-only templates.  UpdateLocalMap maps F.mvpMapPoints to indices, makes ONE call to sivo_localmap_update and writes back as the
 // reference does: the cleared slots of the frame (:1139), both vectors, mnTrackReferenceForFrame of every listed keyframe and point
 // (:1120, :1171, :1200, :1215, :1225), and pReferenceKF and F.mpReferenceKF where a keyframe had the most votes (:1231-1234).
@@ -29,11 +33,19 @@
 // as well — and makes one call.  Indices are stable: an object keeps its index until the next Rebuild, which also compacts.  Whatever
 // changed and was not touched is stale until it is touched or the map is rebuilt.  One mutex guards the pointer <-> index maps: Sync runs
 // on the local mapper's thread, UpdateLocalMap on the tracking thread.
+//
+// With KeepAttributes() the handle's attribute store follows the same rules: Rebuild sends every point's attributes, Sync re-sends those
+// of every point whose row it sends (touched or appended) in one sivo_localmap_set_points behind the apply, and TouchGeometry(pMP) is for
+// the callers that change what the store holds without changing the graph: SetWorldPos, UpdateNormalAndDepth and
+// ComputeDistinctiveDescriptors after a bundle adjustment, a loop correction or a refresh.  A point that moved and was not touched is
+// stale on the device until it is.  MapPoint members read for it: GetWorldPos, GetNormal, GetMinDistance, GetMaxDistance, GetDescriptor,
+// Observations (the getters TrackingAdapter.h asks for).
 #ifndef SIVO_AMD_API_LOCALMAPADAPTER_H
 #define SIVO_AMD_API_LOCALMAPADAPTER_H
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -68,7 +80,7 @@ class LocalMapDevice {
     // them holds.  A covisible, child, parent or observer outside the vector is an error.
     void Rebuild(const std::vector<KeyFrameT *> &vpAllKFs) {
         std::lock_guard<std::mutex> lock(mMutex);
-        mTouchedKFs.clear(); mTouchedPoints.clear();
+        mTouchedKFs.clear(); mTouchedPoints.clear(); mTouchedGeometry.clear();
         mvpKFs = vpAllKFs;
         mKFIndex.clear(); mvpPoints.clear(); mPointIndex.clear();
         const size_t K = mvpKFs.size();
@@ -115,7 +127,30 @@ class LocalMapDevice {
         if (mHandle) localmap_detail::check(sivo_localmap_replace(mHandle, &t), "LocalMapDevice::Rebuild");
         else localmap_detail::check(sivo_localmap_create(&t, &mHandle), "LocalMapDevice::Rebuild");
         mSlotOff.swap(slotOff);
+        if (mReadPoint) {                                              // every row: a replace unsets them all
+            std::vector<int32_t> all(mvpPoints.size());
+            for (size_t p = 0; p < all.size(); ++p) all[p] = (int32_t)p;
+            mSendAttributes(all, "LocalMapDevice::Rebuild");
+        }
     }
+
+    // From the next Rebuild on the handle keeps the attributes of every point.  (A member template, so that a MapPoint without the six
+    // getters still serves a LocalMapDevice that is never asked to keep them.)
+    template <class Unused = void>
+    void KeepAttributes() {
+        std::lock_guard<std::mutex> lock(mMutex);
+        mReadPoint = [](MapPointT *pMP, float *X, float *N, float *range, uint8_t *desc, int32_t *nObs) {
+            const auto P = pMP->GetWorldPos();
+            const auto Pn = pMP->GetNormal();
+            for (int k = 0; k < 3; ++k) { X[k] = P.template at<float>(k, 0); N[k] = Pn.template at<float>(k, 0); }
+            range[0] = pMP->GetMinDistance(); range[1] = pMP->GetMaxDistance();
+            const auto D = pMP->GetDescriptor();
+            std::memcpy(desc, D.ptr(0), 32);
+            *nObs = (int32_t)pMP->Observations();
+        };
+        mSendAttributes = [this](const std::vector<int32_t> &idx, const char *who) { this->template SendAttributesNow<Unused>(idx, who); };
+    }
+    bool KeepsAttributes() const { return (bool)mReadPoint; }
 
     void MarkBad(KeyFrameT *pKF) {
         std::lock_guard<std::mutex> lock(mMutex);
@@ -140,6 +175,11 @@ class LocalMapDevice {
         std::lock_guard<std::mutex> lock(mMutex);
         if (pMP) mTouchedPoints.insert(pMP);
     }
+    // A point whose position, normal, distance range or descriptor changed while its observations did not.
+    void TouchGeometry(MapPointT *pMP) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        if (pMP) mTouchedGeometry.insert(pMP);
+    }
     // The keyframe, the points in its slots and its covisibles: what ProcessNewKeyFrame, CreateNewMapPoints and SearchInNeighbors change.
     void TouchNeighbourhood(KeyFrameT *pKF) {
         if (!pKF) return;
@@ -156,8 +196,15 @@ class LocalMapDevice {
     // The rows of everything touched, and of everything new they lead to, in ONE sivo_localmap_apply; nothing touched: no call.
     void Sync() {
         std::lock_guard<std::mutex> lock(mMutex);
-        if (mTouchedKFs.empty() && mTouchedPoints.empty()) return;
+        if (mTouchedKFs.empty() && mTouchedPoints.empty() && mTouchedGeometry.empty()) return;
         if (!mHandle) throw std::invalid_argument("LocalMapDevice::Sync: Rebuild has not run");
+        for (MapPointT *pMP : mTouchedGeometry)                         // a point the handle does not know is appended with its row
+            if (!mPointIndex.count(pMP)) mTouchedPoints.insert(pMP);
+        if (mTouchedKFs.empty() && mTouchedPoints.empty()) {           // geometry alone: no row of the graph changes
+            SendTouchedAttributes(std::set<int32_t>());
+            mTouchedGeometry.clear();
+            return;
+        }
         const size_t K0 = mvpKFs.size(), P0 = mvpPoints.size();
         struct KfRow { uint8_t bad; int32_t parent; std::vector<int32_t> slots, covis, children; };
         std::map<int32_t, KfRow> kfRows;                               // by index: the delta lists its rows in increasing order
@@ -249,7 +296,10 @@ class LocalMapDevice {
             mvpKFs.resize(K0); mvpPoints.resize(P0);
             throw;
         }
-        mTouchedKFs.clear(); mTouchedPoints.clear();
+        std::set<int32_t> sent;                                         // the points whose row went up: their attributes follow
+        for (const auto &e : pointRows) sent.insert(e.first);
+        SendTouchedAttributes(sent);
+        mTouchedKFs.clear(); mTouchedPoints.clear(); mTouchedGeometry.clear();
     }
 
     // What Optimizer::LocalBundleAdjustment has built when it starts to optimise (reference src/orbslam/Optimizer.cc:496-559, :651-670):
@@ -317,6 +367,30 @@ class LocalMapDevice {
         return it->second;
     }
 
+    // the attributes of the listed points (strictly increasing indices) in ONE sivo_localmap_set_points; the caller holds mMutex.  (Reached
+    // through mSendAttributes alone, which KeepAttributes() sets: a program that never keeps attributes does not need the entry point.)
+    template <class Unused>
+    void SendAttributesNow(const std::vector<int32_t> &idx, const char *who) {
+        const size_t n = idx.size();
+        if (n == 0) return;
+        std::vector<float> pos(3 * n), normal(3 * n), lo(n), hi(n);
+        std::vector<uint8_t> desc(32 * n);
+        std::vector<int32_t> nObs(n);
+        for (size_t i = 0; i < n; ++i) {
+            float range[2];
+            mReadPoint(mvpPoints[(size_t)idx[i]], &pos[3 * i], &normal[3 * i], range, &desc[32 * i], &nObs[i]);
+            lo[i] = range[0]; hi[i] = range[1];
+        }
+        localmap_detail::check(sivo_localmap_set_points(mHandle, (int)n, idx.data(), pos.data(), normal.data(), lo.data(), hi.data(), desc.data(),
+                                                        nObs.data()),
+                               who);
+    }
+    void SendTouchedAttributes(std::set<int32_t> idx) {
+        if (!mReadPoint) return;
+        for (MapPointT *pMP : mTouchedGeometry) idx.insert(mPointIndex.at(pMP));
+        mSendAttributes(std::vector<int32_t>(idx.begin(), idx.end()), "LocalMapDevice::Sync");
+    }
+
     sivo_localmap_t mHandle = nullptr;
     std::vector<KeyFrameT *> mvpKFs;
     std::map<KeyFrameT *, int32_t> mKFIndex;
@@ -325,64 +399,88 @@ class LocalMapDevice {
     std::vector<int64_t> mSlotOff;          // the slot counts: they bound the point list of a call
     std::mutex mMutex;                      // guards the maps above and the sets below
     std::set<KeyFrameT *> mTouchedKFs;
-    std::set<MapPointT *> mTouchedPoints;
+    std::set<MapPointT *> mTouchedPoints, mTouchedGeometry;
+    std::function<void(MapPointT *, float *, float *, float *, uint8_t *, int32_t *)> mReadPoint;      // both set by KeepAttributes()
+    std::function<void(const std::vector<int32_t> &, const char *)> mSendAttributes;
     std::vector<int32_t> mWinLocalKf, mWinFixedKf, mWinLocalPoint, mWinEdgePose, mWinEdgeSlot;      // BAWindow's output buffers
     std::vector<int64_t> mWinEdgeOff;
 };
 
-// In place of UpdateLocalKeyFrames(); UpdateLocalPoints(); (Tracking.cc:1092-1093).  Every keyframe and point of the handle is asked for
-// mnTrackReferenceForFrame == F.mnId, as the reference asks whatever it meets (:1114, :1198, :1213, :1223).
+namespace localmap_detail {
+
+// the arguments and the output buffers of sivo_localmap_update for one frame; the caller holds dev.mMutex
+template <class KeyFrameT, class MapPointT, class FrameT>
+struct UpdateCall {
+    std::vector<int32_t> framePoint, kfMarked, pointMarked, prev, localKf, localPoint;
+    std::vector<uint8_t> cleared;
+    int32_t voted = 0, nLocalKf = 0, refKf = -1, nLocalPoints = 0;
+
+    // Every keyframe and point of the handle is asked for mnTrackReferenceForFrame == F.mnId, as the reference asks whatever it meets
+    // (:1114, :1198, :1213, :1223).
+    UpdateCall(LocalMapDevice<KeyFrameT, MapPointT> &dev, FrameT &F, const std::vector<KeyFrameT *> &vpLocalKeyFrames, const char *who) {
+        const size_t S = (size_t)F.numSemanticKeys;
+        framePoint.assign(S, -1);
+        for (size_t i = 0; i < S; ++i) {
+            MapPointT *pMP = F.mvpMapPoints[i];
+            if (!pMP) continue;
+            const auto it = dev.mPointIndex.find(pMP);
+            if (it == dev.mPointIndex.end())
+                throw std::runtime_error(std::string(who) + ": frame slot " + std::to_string(i) + " holds a map point the device map does not know (created after the last Rebuild)");
+            framePoint[i] = it->second;
+        }
+        for (KeyFrameT *pKF : vpLocalKeyFrames) prev.push_back(dev.Known(pKF, "local keyframe"));
+        for (size_t k = 0; k < dev.mvpKFs.size(); ++k)
+            if (dev.mvpKFs[k]->mnTrackReferenceForFrame == F.mnId) kfMarked.push_back((int32_t)k);
+        for (size_t p = 0; p < dev.mvpPoints.size(); ++p)
+            if (dev.mvpPoints[p]->mnTrackReferenceForFrame == F.mnId) pointMarked.push_back((int32_t)p);
+        int64_t gPrev = 0;
+        for (int32_t k : prev) gPrev += dev.mSlotOff[(size_t)k + 1] - dev.mSlotOff[(size_t)k];
+        const size_t pointCap = (size_t)std::min<int64_t>((int64_t)dev.mvpPoints.size(), std::max<int64_t>(dev.mSlotOff.back(), gPrev));
+        localKf.resize(dev.mvpKFs.size()); localPoint.resize(pointCap);
+        cleared.assign(S, 0);
+    }
+
+    // what the reference leaves behind (:1139, :1150-1172, :1200, :1215, :1225, :1231-1234, :1097-1120)
+    void WriteBack(LocalMapDevice<KeyFrameT, MapPointT> &dev, FrameT &F, std::vector<KeyFrameT *> &vpLocalKeyFrames,
+                   std::vector<MapPointT *> &vpLocalMapPoints, KeyFrameT *&pReferenceKF) const {
+        for (size_t i = 0; i < cleared.size(); ++i)
+            if (cleared[i]) F.mvpMapPoints[i] = static_cast<MapPointT *>(nullptr);      // (:1139)
+        if (voted) {                                                                    // (:1144-1145: else the list stays)
+            vpLocalKeyFrames.clear();                                                   // (:1150)
+            for (int32_t j = 0; j < nLocalKf; ++j) {
+                KeyFrameT *pKF = dev.mvpKFs[(size_t)localKf[(size_t)j]];
+                vpLocalKeyFrames.push_back(pKF);
+                pKF->mnTrackReferenceForFrame = F.mnId;                                 // (:1171, :1200, :1215, :1225)
+            }
+            if (refKf >= 0) {                                                           // (:1231-1234)
+                pReferenceKF = dev.mvpKFs[(size_t)refKf];
+                F.mpReferenceKF = pReferenceKF;
+            }
+        }
+        vpLocalMapPoints.clear();                                                       // (:1097)
+        for (int32_t j = 0; j < nLocalPoints; ++j) {
+            MapPointT *pMP = dev.mvpPoints[(size_t)localPoint[(size_t)j]];
+            vpLocalMapPoints.push_back(pMP);                                            // (:1119)
+            pMP->mnTrackReferenceForFrame = F.mnId;                                     // (:1120)
+        }
+    }
+};
+
+}  // namespace localmap_detail
+
+// In place of UpdateLocalKeyFrames(); UpdateLocalPoints(); (Tracking.cc:1092-1093).
 template <class KeyFrameT, class MapPointT, class FrameT>
 void UpdateLocalMap(LocalMapDevice<KeyFrameT, MapPointT> &dev, FrameT &F, std::vector<KeyFrameT *> &vpLocalKeyFrames,
                     std::vector<MapPointT *> &vpLocalMapPoints, KeyFrameT *&pReferenceKF) {
     std::lock_guard<std::mutex> lock(dev.mMutex);                  // the whole call: it sees the map before a Sync or after it
     if (!dev.mHandle) throw std::invalid_argument("UpdateLocalMap: Rebuild has not run");
-    const size_t S = (size_t)F.numSemanticKeys;
-    std::vector<int32_t> framePoint(S, -1), kfMarked, pointMarked, prev;
-    for (size_t i = 0; i < S; ++i) {
-        MapPointT *pMP = F.mvpMapPoints[i];
-        if (!pMP) continue;
-        const auto it = dev.mPointIndex.find(pMP);
-        if (it == dev.mPointIndex.end())
-            throw std::runtime_error("UpdateLocalMap: frame slot " + std::to_string(i) + " holds a map point the device map does not know (created after the last Rebuild)");
-        framePoint[i] = it->second;
-    }
-    for (KeyFrameT *pKF : vpLocalKeyFrames) prev.push_back(dev.Known(pKF, "local keyframe"));
-    for (size_t k = 0; k < dev.mvpKFs.size(); ++k)
-        if (dev.mvpKFs[k]->mnTrackReferenceForFrame == F.mnId) kfMarked.push_back((int32_t)k);
-    for (size_t p = 0; p < dev.mvpPoints.size(); ++p)
-        if (dev.mvpPoints[p]->mnTrackReferenceForFrame == F.mnId) pointMarked.push_back((int32_t)p);
-    int64_t gPrev = 0;
-    for (int32_t k : prev) gPrev += dev.mSlotOff[(size_t)k + 1] - dev.mSlotOff[(size_t)k];
-    const size_t K = dev.mvpKFs.size();
-    const size_t pointCap = (size_t)std::min<int64_t>((int64_t)dev.mvpPoints.size(), std::max<int64_t>(dev.mSlotOff.back(), gPrev));
-    std::vector<int32_t> localKf(K), localPoint(pointCap);
-    std::vector<uint8_t> cleared(S, 0);
-    int32_t voted = 0, nLocalKf = 0, refKf = -1, nLocalPoints = 0;
-    localmap_detail::check(sivo_localmap_update(dev.mHandle, (int)S, framePoint.data(), (int)kfMarked.size(), kfMarked.data(), (int)pointMarked.size(),
-                                                pointMarked.data(), (int)prev.size(), prev.data(), &voted, cleared.data(), (int)K, localKf.data(),
-                                                &nLocalKf, &refKf, (int)pointCap, localPoint.data(), &nLocalPoints, nullptr),
+    localmap_detail::UpdateCall<KeyFrameT, MapPointT, FrameT> c(dev, F, vpLocalKeyFrames, "UpdateLocalMap");
+    localmap_detail::check(sivo_localmap_update(dev.mHandle, (int)c.framePoint.size(), c.framePoint.data(), (int)c.kfMarked.size(), c.kfMarked.data(),
+                                                (int)c.pointMarked.size(), c.pointMarked.data(), (int)c.prev.size(), c.prev.data(), &c.voted,
+                                                c.cleared.data(), (int)c.localKf.size(), c.localKf.data(), &c.nLocalKf, &c.refKf,
+                                                (int)c.localPoint.size(), c.localPoint.data(), &c.nLocalPoints, nullptr),
                            "UpdateLocalMap");
-    for (size_t i = 0; i < S; ++i)
-        if (cleared[i]) F.mvpMapPoints[i] = static_cast<MapPointT *>(nullptr);      // (:1139)
-    if (voted) {                                                                    // (:1144-1145: else the list stays)
-        vpLocalKeyFrames.clear();                                                   // (:1150)
-        for (int32_t j = 0; j < nLocalKf; ++j) {
-            KeyFrameT *pKF = dev.mvpKFs[(size_t)localKf[(size_t)j]];
-            vpLocalKeyFrames.push_back(pKF);
-            pKF->mnTrackReferenceForFrame = F.mnId;                                 // (:1171, :1200, :1215, :1225)
-        }
-        if (refKf >= 0) {                                                           // (:1231-1234)
-            pReferenceKF = dev.mvpKFs[(size_t)refKf];
-            F.mpReferenceKF = pReferenceKF;
-        }
-    }
-    vpLocalMapPoints.clear();                                                       // (:1097)
-    for (int32_t j = 0; j < nLocalPoints; ++j) {
-        MapPointT *pMP = dev.mvpPoints[(size_t)localPoint[(size_t)j]];
-        vpLocalMapPoints.push_back(pMP);                                            // (:1119)
-        pMP->mnTrackReferenceForFrame = F.mnId;                                     // (:1120)
-    }
+    c.WriteBack(dev, F, vpLocalKeyFrames, vpLocalMapPoints, pReferenceKF);
 }
 
 }  // namespace SIVO

@@ -1,6 +1,9 @@
 // The step the tracking thread takes on every frame between its two pose optimisations, over the SLAM object graph:
 //     bool isInFrustum(F, pMP, viewingCosLimit)            Frame::isInFrustum, reference src/orbslam/Frame.cc:267-324, on the host
 //     int  SearchLocalPoints(F, vpLocalMapPoints, th)      Tracking::SearchLocalPoints, src/orbslam/Tracking.cc:1033-1085
+//     int  TrackLocalMapSearch(dev, F, vpLocalKeyFrames, vpLocalMapPoints, pReferenceKF, th)
+//                                                          UpdateLocalMap() and SearchLocalPoints() of Tracking::TrackLocalMap (:1087-1124,
+//                                                          :1033-1085) in ONE call on the resident map of LocalMapAdapter.h
 // as header-only templates.  SearchLocalPoints runs the reference's first loop over the frame's own points as it stands, gathers the local
 // map into arrays, makes ONE call to sivo_search_local_points — the device culls every point with isInFrustum's arithmetic, writes the
 // query of every point in view and runs ORBmatcher::SearchByProjection's matching on them (sivo_amd/csrc/frustum_math.hpp, search.hip) —
@@ -22,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "LocalMapAdapter.h"
 #include "ORBmatcher.h"
 #include "../../csrc/frustum_math.hpp"
 
@@ -138,6 +142,66 @@ int SearchLocalPoints(FrameT &F, const std::vector<MapPointT *> &vpLocalMapPoint
     if (nToMatch == 0) return 0;                                        // (:1072)
     for (int k = 0; k < dF.size(); ++k)
         if (match[k] >= 0) F.mvpMapPoints[k] = vpLocalMapPoints[match[k]];
+    return nmatches;
+}
+
+// SIVO::UpdateLocalMap followed by SIVO::SearchLocalPoints, with every side effect of that pair in the same place — the frame's cleared
+// slots, both vectors, mnTrackReferenceForFrame, pReferenceKF and F.mpReferenceKF; IncreaseVisible, mnLastFrameSeen and mbTrackInView of
+// the frame's own points; mbTrackInView, the mTrack* fields and IncreaseVisible of the local points; the matches in F.mvpMapPoints —
+// from ONE sivo_localmap_search_local_points: no MapPoint of the local map is read on the host, their attributes are the ones the
+// handle keeps (dev.KeepAttributes() before Rebuild; Touch / TouchGeometry and Sync keep them current, and a point that moved without
+// either is stale).  seen_point — the points whose mnLastFrameSeen already equals F.mnId when the call starts, such as the outliers
+// dropped at Tracking.cc:626-630 — is gathered by one walk over the handle's points that reads mnLastFrameSeen, a field only the
+// tracking thread writes, beside the mnTrackReferenceForFrame the update's premarks are read from.  isBad() is the handle's (MarkBad,
+// Touch), as in UpdateLocalMap.  Returns what SearchByProjection returns, 0 when no point is in view; *pnToMatch = nToMatch.
+template <class KeyFrameT, class MapPointT, class FrameT>
+int TrackLocalMapSearch(LocalMapDevice<KeyFrameT, MapPointT> &dev, FrameT &F, std::vector<KeyFrameT *> &vpLocalKeyFrames,
+                        std::vector<MapPointT *> &vpLocalMapPoints, KeyFrameT *&pReferenceKF, float th, float nnratio = 0.8f,
+                        int *pnToMatch = nullptr) {
+    using namespace matcher_detail;
+    std::lock_guard<std::mutex> lock(dev.mMutex);                  // the whole call: it sees the map before a Sync or after it
+    if (!dev.mHandle) throw std::invalid_argument("TrackLocalMapSearch: Rebuild has not run");
+    if (!dev.KeepsAttributes()) throw std::invalid_argument("TrackLocalMapSearch: the device map keeps no attributes (KeepAttributes() before Rebuild)");
+    localmap_detail::UpdateCall<KeyFrameT, MapPointT, FrameT> c(dev, F, vpLocalKeyFrames, "TrackLocalMapSearch");
+    std::vector<int32_t> seen;
+    for (size_t p = 0; p < dev.mvpPoints.size(); ++p)
+        if (dev.mvpPoints[p]->mnLastFrameSeen == F.mnId) seen.push_back((int32_t)p);
+    const SivoFrustum fr = tracking_detail::frustum_of(F, 0.5f);
+    FrameLease dF(F);
+    const size_t n = c.localPoint.size();
+    std::vector<uint8_t> status(n, 0);
+    std::vector<float> px(n, 0.f), py(n, 0.f), pxr(n, 0.f), viewCos(n, 0.f);
+    std::vector<int32_t> level(n, 0), match((size_t)dF.size(), -1);
+    int nToMatch = 0, nmatches = 0;
+    tracking_detail::check(
+        sivo_localmap_search_local_points(dev.mHandle, dF.get(), &fr, (int)c.framePoint.size(), c.framePoint.data(), (int)c.kfMarked.size(),
+                                          c.kfMarked.data(), (int)c.pointMarked.size(), c.pointMarked.data(), (int)c.prev.size(), c.prev.data(),
+                                          (int)seen.size(), seen.data(), th, nnratio, &c.voted, c.cleared.data(), (int)c.localKf.size(),
+                                          c.localKf.data(), &c.nLocalKf, &c.refKf, (int)c.localPoint.size(), c.localPoint.data(), &c.nLocalPoints,
+                                          nullptr, status.data(), px.data(), py.data(), pxr.data(), viewCos.data(), level.data(), match.data(),
+                                          &nToMatch, &nmatches),
+        "TrackLocalMapSearch");
+    c.WriteBack(dev, F, vpLocalKeyFrames, vpLocalMapPoints, pReferenceKF);
+    // Do not search map points already matched (:1035-1049); the slots of the bad ones are cleared already (:1139)
+    for (auto vit = F.mvpMapPoints.begin(), vend = F.mvpMapPoints.end(); vit != vend; vit++) {
+        MapPointT *pMP = *vit;
+        if (!pMP) continue;
+        pMP->IncreaseVisible();
+        pMP->mnLastFrameSeen = F.mnId;
+        pMP->mbTrackInView = false;
+    }
+    for (size_t i = 0; i < vpLocalMapPoints.size(); ++i) {                 // (:1054-1070)
+        MapPointT *pMP = vpLocalMapPoints[i];
+        if (status[i] == SIVO_FRUSTUM_SKIPPED) continue;
+        pMP->mbTrackInView = false;                                     // (Frame.cc:268)
+        if (status[i] != SIVO_FRUSTUM_IN_VIEW) continue;
+        tracking_detail::write_track(pMP, px[i], py[i], pxr[i], viewCos[i], level[i]);
+        pMP->IncreaseVisible();
+    }
+    if (pnToMatch) *pnToMatch = nToMatch;
+    if (nToMatch == 0) return 0;                                        // (:1072)
+    for (int k = 0; k < dF.size(); ++k)
+        if (match[k] >= 0) F.mvpMapPoints[k] = vpLocalMapPoints[(size_t)match[k]];
     return nmatches;
 }
 

@@ -341,6 +341,8 @@ static void lm_load(sivo_localmap *m, const SivoLocalMapTables &t) {
     L.place(m->dev(m->cur).reserve(L.bytes()), host.data());
     L.send(c.stream);
     SIVO_HIP(hipStreamSynchronize(c.stream));
+    m->attr_reserve(P, 0, c.stream);                                    // (no row survives: the caller may have renumbered)
+    m->attr_unset_all(P);
     m->d = d;
     m->first = first;
     m->slot_off.assign(K + 1, 0);
@@ -386,6 +388,7 @@ extern "C" int sivo_localmap_destroy(sivo_localmap_t m) {
             DeviceGuard dg(m->device);
             m->dev(0).release();
             m->dev(1).release();
+            m->attr_release();
         }
         delete m;
         return SIVO_OK;
@@ -424,6 +427,56 @@ extern "C" int sivo_localmap_set_bad(sivo_localmap_t m, int n_points, const int3
     });
 }
 
+// The device part of sivo_localmap_update (localmap_handle.hpp): the caller holds the handle's mutex and has checked the arguments.
+int sivo::lm_run_update(sivo_localmap *m, const LmUpdateArgs &u, int64_t g_prev, const char *who, LmUpdateHook *hook, LmCall *call) {
+    require_device();
+    DeviceGuard dg(m->device);
+    SolverCtx &c = lm_ctx();
+    const size_t K = (size_t)m->d.n_kf, P = (size_t)m->d.n_points, S = (size_t)u.n_slots;
+    const int64_t g_max = std::max(m->total_slots, g_prev);             // no list the point passes walk holds more slots
+    const unsigned nb = (unsigned)std::max<int64_t>(1, cdiv64(g_max, LP_THREADS));
+    LmCall a;
+    a.t = m->d; a.first = m->first;
+    a.n_slots = u.n_slots; a.n_kf_pre = u.n_kf_premarked; a.n_pt_pre = u.n_point_premarked; a.n_prev = u.n_prev;
+    a.point_cap = (int)std::min<int64_t>(u.point_capacity, std::min<int64_t>((int64_t)P, g_max));
+    Layout L;
+    L.copy(a.frame_point, u.frame_point, 4 * S); L.copy(a.kf_pre, u.kf_premarked, 4 * (size_t)u.n_kf_premarked);
+    L.copy(a.pt_pre, u.point_premarked, 4 * (size_t)u.n_point_premarked); L.copy(a.prev, u.prev_local_kf, 4 * (size_t)u.n_prev);
+    L.zero(a.marks_g, K > SIVO_COVIS_LDS_KF ? 4 * ((K + 31) / 32) : 0); L.zero(a.counts, 4 * K);
+    L.take(a.hdr, 4 * LM_HDR_WORDS); L.take(a.slot_cleared, S); L.take(a.local_kf, 4 * K); L.take(a.local_point, 4 * (size_t)a.point_cap);
+    L.take(a.list_off, 4 * (std::max(K, (size_t)u.n_prev) + 1)); L.take(a.block_sum, 4 * (size_t)nb);       // scratch: not copied back
+    if (hook) hook->regions(L);
+    L.place(c.dev.reserve(L.bytes()), c.in.reserve(L.bytes()));
+    L.send(c.stream);
+    if (P) SIVO_HIP(hipMemsetAsync(m->first, 0xFF, 4 * P, c.stream));
+    hipLaunchKernelGGL(localmap_vote_kernel, dim3(1), dim3(LV_THREADS), 0, c.stream, a);
+    hipLaunchKernelGGL(localmap_select_kernel, dim3(1), dim3(LS_THREADS), 0, c.stream, a);
+    hipLaunchKernelGGL(localmap_first_kernel, dim3(nb), dim3(LP_THREADS), 0, c.stream, a);
+    hipLaunchKernelGGL(localmap_count_kernel, dim3(nb), dim3(LP_THREADS), 0, c.stream, a);
+    hipLaunchKernelGGL(localmap_scatter_kernel, dim3(nb), dim3(LP_THREADS), 0, c.stream, a);
+    SIVO_HIP(hipGetLastError());
+    if (hook) hook->launch(a, c.stream);
+    const size_t down = (size_t)((const char *)a.local_point - (const char *)a.counts) + 4 * (size_t)a.point_cap;
+    SIVO_HIP(hipMemcpyAsync(L.host(a.counts), a.counts, down, hipMemcpyDeviceToHost, c.stream));
+    SIVO_HIP(hipStreamSynchronize(c.stream));
+    const int32_t *hdr = L.host(a.hdr);
+    const int32_t v = hdr[LM_HDR_VOTED], nk = hdr[LM_HDR_N_KF], np = hdr[LM_HDR_N_POINTS];
+    if (v && nk > u.kf_capacity) return fail(SIVO_ERR_CAPACITY, "%s: %d local keyframes, capacity %d", who, nk, u.kf_capacity);
+    if (np > u.point_capacity) return fail(SIVO_ERR_CAPACITY, "%s: %d local map points, capacity %d", who, np, u.point_capacity);
+    *u.voted = v;
+    if (S) std::memcpy(u.slot_cleared, L.host(a.slot_cleared), S);
+    if (v) {
+        *u.n_local_kf = nk;
+        if (nk) std::memcpy(u.local_kf, L.host(a.local_kf), 4 * (size_t)nk);
+    }
+    *u.ref_kf = hdr[LM_HDR_REF];
+    *u.n_local_points = np;
+    if (np) std::memcpy(u.local_point, L.host(a.local_point), 4 * (size_t)np);
+    if (u.counts && K) std::memcpy(u.counts, L.host(a.counts), 4 * K);
+    if (call) *call = a;
+    return SIVO_OK;
+}
+
 extern "C" int sivo_localmap_update(sivo_localmap_t m, int n_slots, const int32_t *frame_point, int n_kf_premarked,
                                     const int32_t *kf_premarked, int n_point_premarked, const int32_t *point_premarked, int n_prev,
                                     const int32_t *prev_local_kf, int32_t *voted, uint8_t *slot_cleared, int kf_capacity,
@@ -437,49 +490,9 @@ extern "C" int sivo_localmap_update(sivo_localmap_t m, int n_slots, const int32_
                  lm_check_update(m->d.n_kf, m->d.n_points, m->slot_off.data(), n_slots, frame_point, n_kf_premarked, kf_premarked, n_point_premarked,
                                  point_premarked, n_prev, prev_local_kf, voted, slot_cleared, kf_capacity, local_kf, n_local_kf, ref_kf,
                                  point_capacity, local_point, n_local_points, &g_prev));
-        require_device();
-        DeviceGuard dg(m->device);
-        SolverCtx &c = lm_ctx();
-        const size_t K = (size_t)m->d.n_kf, P = (size_t)m->d.n_points, S = (size_t)n_slots;
-        const int64_t g_max = std::max(m->total_slots, g_prev);         // no list the point passes walk holds more slots
-        const unsigned nb = (unsigned)std::max<int64_t>(1, cdiv64(g_max, LP_THREADS));
-        LmCall a;
-        a.t = m->d; a.first = m->first;
-        a.n_slots = n_slots; a.n_kf_pre = n_kf_premarked; a.n_pt_pre = n_point_premarked; a.n_prev = n_prev;
-        a.point_cap = (int)std::min<int64_t>(point_capacity, std::min<int64_t>((int64_t)P, g_max));
-        Layout L;
-        L.copy(a.frame_point, frame_point, 4 * S); L.copy(a.kf_pre, kf_premarked, 4 * (size_t)n_kf_premarked);
-        L.copy(a.pt_pre, point_premarked, 4 * (size_t)n_point_premarked); L.copy(a.prev, prev_local_kf, 4 * (size_t)n_prev);
-        L.zero(a.marks_g, K > SIVO_COVIS_LDS_KF ? 4 * ((K + 31) / 32) : 0); L.zero(a.counts, 4 * K);
-        L.take(a.hdr, 4 * LM_HDR_WORDS); L.take(a.slot_cleared, S); L.take(a.local_kf, 4 * K); L.take(a.local_point, 4 * (size_t)a.point_cap);
-        L.take(a.list_off, 4 * (std::max(K, (size_t)n_prev) + 1)); L.take(a.block_sum, 4 * (size_t)nb);       // scratch: not copied back
-        L.place(c.dev.reserve(L.bytes()), c.in.reserve(L.bytes()));
-        L.send(c.stream);
-        if (P) SIVO_HIP(hipMemsetAsync(m->first, 0xFF, 4 * P, c.stream));
-        hipLaunchKernelGGL(localmap_vote_kernel, dim3(1), dim3(LV_THREADS), 0, c.stream, a);
-        hipLaunchKernelGGL(localmap_select_kernel, dim3(1), dim3(LS_THREADS), 0, c.stream, a);
-        hipLaunchKernelGGL(localmap_first_kernel, dim3(nb), dim3(LP_THREADS), 0, c.stream, a);
-        hipLaunchKernelGGL(localmap_count_kernel, dim3(nb), dim3(LP_THREADS), 0, c.stream, a);
-        hipLaunchKernelGGL(localmap_scatter_kernel, dim3(nb), dim3(LP_THREADS), 0, c.stream, a);
-        SIVO_HIP(hipGetLastError());
-        const size_t down = (size_t)((const char *)a.local_point - (const char *)a.counts) + 4 * (size_t)a.point_cap;
-        SIVO_HIP(hipMemcpyAsync(L.host(a.counts), a.counts, down, hipMemcpyDeviceToHost, c.stream));
-        SIVO_HIP(hipStreamSynchronize(c.stream));
-        const int32_t *hdr = L.host(a.hdr);
-        const int32_t v = hdr[LM_HDR_VOTED], nk = hdr[LM_HDR_N_KF], np = hdr[LM_HDR_N_POINTS];
-        if (v && nk > kf_capacity) return fail(SIVO_ERR_CAPACITY, "sivo_localmap_update: %d local keyframes, capacity %d", nk, kf_capacity);
-        if (np > point_capacity) return fail(SIVO_ERR_CAPACITY, "sivo_localmap_update: %d local map points, capacity %d", np, point_capacity);
-        *voted = v;
-        if (S) std::memcpy(slot_cleared, L.host(a.slot_cleared), S);
-        if (v) {
-            *n_local_kf = nk;
-            if (nk) std::memcpy(local_kf, L.host(a.local_kf), 4 * (size_t)nk);
-        }
-        *ref_kf = hdr[LM_HDR_REF];
-        *n_local_points = np;
-        if (np) std::memcpy(local_point, L.host(a.local_point), 4 * (size_t)np);
-        if (counts && K) std::memcpy(counts, L.host(a.counts), 4 * K);
-        return SIVO_OK;
+        const LmUpdateArgs u{n_slots, frame_point, n_kf_premarked, kf_premarked, n_point_premarked, point_premarked, n_prev, prev_local_kf, voted,
+                             slot_cleared, kf_capacity, local_kf, n_local_kf, ref_kf, point_capacity, local_point, n_local_points, counts};
+        return lm_run_update(m, u, g_prev, "sivo_localmap_update", nullptr, nullptr);
     });
 }
 
@@ -533,6 +546,7 @@ extern "C" int sivo_localmap_apply(sivo_localmap_t m, const SivoLocalMapDelta *d
         N.take(n.kf_order, 4 * K1); N.take(first, 4 * P1);
         L.place(c.dev.reserve(L.bytes()), c.in.reserve(L.bytes()));
         N.place(m->dev(1 - m->cur).reserve(N.bytes()), nullptr);
+        m->attr_reserve(P1, P0, c.stream);                              // the stored rows move with a device copy; capacity only
         int64_t *new_off[LMD_TABLES] = {const_cast<int64_t *>(n.obs_off), const_cast<int64_t *>(n.slot_off), const_cast<int64_t *>(n.covis_off),
                                         const_cast<int64_t *>(n.child_off)};
         int32_t *new_val[LMD_TABLES] = {const_cast<int32_t *>(n.obs_kf), const_cast<int32_t *>(n.slot_point), const_cast<int32_t *>(n.covis_kf),
@@ -568,6 +582,7 @@ extern "C" int sivo_localmap_apply(sivo_localmap_t m, const SivoLocalMapDelta *d
         for (int w = 0; w < LMD_TABLES; ++w) m->total[w] = totals[w];   // the exact totals, not the bounds the pools were sized from
         m->d = n;
         m->first = first;
+        m->attr_resize(P1);                                             // appended points are unset
         m->slot_off.swap(slot_off);
         m->total_slots = m->total[LMD_SLOT];
         m->cur = 1 - m->cur;

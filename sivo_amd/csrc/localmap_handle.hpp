@@ -1,5 +1,6 @@
-// localmap_handle.hpp — what localmap.hip and ba_window.hip share: the resident map's handle, the solver context its calls run on, the
-// argument block of the point passes (localmap_first / _count / _scatter_kernel, defined in localmap.hip) and the workgroup scans.
+// localmap_handle.hpp — what localmap.hip, ba_window.hip and localmap_track.hip share: the resident map's handle with its attribute
+// store, the solver context its calls run on, the argument block of the point passes (localmap_first / _count / _scatter_kernel, defined
+// in localmap.hip), the workgroup scans and the device part of sivo_localmap_update as a function (lm_run_update).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +15,7 @@
 
 #include "localmap_math.hpp"
 #include "localmap_delta_math.hpp"
+#include "localmap_track_math.hpp"
 
 namespace sivo {
 
@@ -154,6 +156,29 @@ inline SolverCtx &lm_ctx() {
     return c;
 }
 
+// What a caller of lm_run_update adds to the update: regions of the call's one upload, and launches behind the point passes on the
+// call's stream, before the download and the call's one synchronisation.
+struct LmUpdateHook {
+    virtual void regions(Layout &L) = 0;
+    virtual void launch(const LmCall &a, hipStream_t stream) = 0;
+    virtual ~LmUpdateHook() {}
+};
+
+// the arguments of sivo_localmap_update
+struct LmUpdateArgs {
+    int n_slots; const int32_t *frame_point; int n_kf_premarked; const int32_t *kf_premarked; int n_point_premarked;
+    const int32_t *point_premarked; int n_prev; const int32_t *prev_local_kf; int32_t *voted; uint8_t *slot_cleared; int kf_capacity;
+    int32_t *local_kf, *n_local_kf, *ref_kf; int point_capacity; int32_t *local_point, *n_local_points, *counts;
+};
+
+}  // namespace sivo
+
+struct sivo_localmap;
+namespace sivo {
+// sivo_localmap_update on a handle whose mutex the caller holds, the arguments checked (g_prev from lm_check_update): the upload, the
+// five launches, the hook's, the download, the synchronisation, the outputs.  `who` heads the text of SIVO_ERR_CAPACITY.  `call`
+// receives the call's device pointers, which stay valid on this thread until its next call on a handle.  Defined in localmap.hip.
+int lm_run_update(sivo_localmap *m, const LmUpdateArgs &u, int64_t g_prev, const char *who, LmUpdateHook *hook, LmCall *call);
 }  // namespace sivo
 
 struct sivo_localmap {
@@ -167,4 +192,55 @@ struct sivo_localmap {
     uint32_t *first = nullptr;
     std::vector<int64_t> slot_off;         // host copy: the slot counts bound the grids and size prev_local_kf's walk
     int64_t total_slots = 0;
+
+    // ---- the attribute store (sivo_localmap_set_points): structure-of-arrays over the handle's point indices, in an allocation of its
+    // own (the tables ping-pong between buf_a and buf_b), which grows by a device copy and keeps every stored row
+    char *attr_base = nullptr;
+    size_t attr_cap = 0;                   // rows; a multiple of 64, so every array starts at a multiple of 256 bytes
+    sivo::LtAttrs attr{};                  // device pointers into attr_base
+    std::vector<uint64_t> attr_set;        // one bit per point: a set_points named it since create / replace / its append
+    int64_t n_attr_set = 0;
+
+    static sivo::LtAttrs attr_at(char *base, size_t cap) {
+        sivo::LtAttrs a;
+        a.pos = (float *)base; a.normal = (float *)(base + 12 * cap); a.min_dist = (float *)(base + 24 * cap);
+        a.max_dist = (float *)(base + 28 * cap); a.desc = (uint32_t *)(base + 32 * cap); a.n_obs = (int32_t *)(base + 64 * cap);
+        return a;
+    }
+    // room for n_points rows; the first `keep` rows survive a growth (copied on `stream`, which is synchronised before the old
+    // allocation is freed)
+    void attr_reserve(size_t n_points, size_t keep, hipStream_t stream) {
+        if (n_points <= attr_cap) return;
+        const size_t cap = (std::max<size_t>(2 * n_points, 4096) + 63) / 64 * 64;
+        char *base = nullptr;
+        SIVO_HIP(hipMalloc((void **)&base, sivo::LT_ROW_BYTES * cap));
+        const sivo::LtAttrs n = attr_at(base, cap);
+        try {
+            if (keep && attr_base) {
+                SIVO_HIP(hipMemcpyAsync(n.pos, attr.pos, 12 * keep, hipMemcpyDeviceToDevice, stream));
+                SIVO_HIP(hipMemcpyAsync(n.normal, attr.normal, 12 * keep, hipMemcpyDeviceToDevice, stream));
+                SIVO_HIP(hipMemcpyAsync(n.min_dist, attr.min_dist, 4 * keep, hipMemcpyDeviceToDevice, stream));
+                SIVO_HIP(hipMemcpyAsync(n.max_dist, attr.max_dist, 4 * keep, hipMemcpyDeviceToDevice, stream));
+                SIVO_HIP(hipMemcpyAsync(n.desc, attr.desc, 32 * keep, hipMemcpyDeviceToDevice, stream));
+                SIVO_HIP(hipMemcpyAsync(n.n_obs, attr.n_obs, 4 * keep, hipMemcpyDeviceToDevice, stream));
+                SIVO_HIP(hipStreamSynchronize(stream));
+            }
+        } catch (...) {
+            (void)hipFree(base);
+            throw;
+        }
+        if (attr_base) (void)hipFree(attr_base);
+        attr_base = base; attr_cap = cap; attr = n;
+    }
+    // the bitmap for n_points rows: the rows it already holds keep their bit, new rows are unset
+    void attr_resize(size_t n_points) { attr_set.resize((n_points + 63) / 64, 0); }
+    void attr_unset_all(size_t n_points) {
+        attr_set.assign((n_points + 63) / 64, 0);
+        n_attr_set = 0;
+    }
+    bool attr_is_set(int32_t p) const { return (attr_set[(size_t)p >> 6] >> (p & 63)) & 1u; }
+    void attr_release() {
+        if (attr_base) (void)hipFree(attr_base);
+        attr_base = nullptr; attr_cap = 0;
+    }
 };

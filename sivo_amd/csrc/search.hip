@@ -31,6 +31,7 @@
 #include "common.hpp"
 #include "frustum_math.hpp"
 #include "mframe.hpp"
+#include "search_engine.hpp"
 #include "solver_host.hpp"
 
 #define SIVO_HISTO 30       // ORBmatcher::HISTO_LENGTH
@@ -286,20 +287,7 @@ char *scratch(sivo_mframe &F, size_t bytes) {
     return F.slab->d + F.frame_bytes;
 }
 
-// Queries made on the device (sivo_search_local_points): the producer adds its inputs (copy regions) and its results (take regions) to
-// the engine's layout, enqueues its kernel behind the upload — it writes all nq query records — and reads its own results from the
-// mirror once the engine has synchronised.
-// Contract: with nq > 0 the engine calls regions, launch and collect, once each and in that order; with nq <= 0 it returns before it
-// takes any scratch and calls none of them (there is nothing to stage or collect).  scratch() may move the frame to a bigger slab, so
-// the frame's view and its stream are valid only from launch on: launch takes them from the frame it is handed, never from a copy made
-// before run_search.
-struct DeviceQueries {
-    virtual void regions(Layout &L) = 0;
-    virtual void launch(const sivo_mframe &F, SivoSearchQuery *d_q) = 0;
-    virtual void collect(const Layout &L) = 0;
-    virtual ~DeviceQueries() {}
-};
-
+// (DeviceQueries, the interface of a producer that makes the queries on the device, is search_engine.hpp)
 struct EngineIn {                // the host arrays of a call (all null where only the size of the layout is asked for)
     const SivoSearchQuery *q;
     const uint8_t *qdesc;
@@ -316,14 +304,19 @@ struct EngineBufs {              // what the layout hands out beside the pointer
 // The engine's regions of one call, the only statement of its scratch: [ upload | results | device-only ].  The upload holds the
 // queries, their descriptors, the candidate lists (`lists`), the blocked flags and the regions that START with a value the caller
 // writes through L.host() — pick, flags and, for a dynamic rule, owner[0] and npick; the results hold the producer's as well.
+// A producer with device_inputs() writes the queries, their descriptors and the blocked flags on the device: they move behind the
+// results, and the candidate ranges (read with lists only) take no room.
 void engine_layout(Layout &L, SearchArgs &a, EngineBufs &b, int n, int nq, int n_cand, bool dynamic, bool lists, DeviceQueries *dq,
                    const EngineIn &in = EngineIn{}) {
     const size_t N = (size_t)n, Q = (size_t)nq;
-    L.copy(b.q, in.q, Q * sizeof(SivoSearchQuery));                 // (with dq: written by its kernel)
-    L.copy(a.qdesc, in.qdesc, 32 * Q);
-    L.copy(a.cbeg, in.cbeg, 4 * Q); L.copy(a.cend, in.cend, 4 * Q);     // (read with lists only; their room is part of a call's size)
-    if (lists) L.copy(a.cidx, in.cidx, 4 * (size_t)n_cand);
-    L.copy(a.blocked, in.blocked, N);
+    const bool on_device = dq && dq->device_inputs() && !lists;
+    if (!on_device) {
+        L.copy(b.q, in.q, Q * sizeof(SivoSearchQuery));             // (with dq: written by its kernel)
+        L.copy(a.qdesc, in.qdesc, 32 * Q);
+        L.copy(a.cbeg, in.cbeg, 4 * Q); L.copy(a.cend, in.cend, 4 * Q); // (read with lists only; their room is part of a call's size)
+        if (lists) L.copy(a.cidx, in.cidx, 4 * (size_t)n_cand);
+        L.copy(a.blocked, in.blocked, N);
+    }
     L.copy(a.pick, nullptr, 4 * Q);                                 // -1
     if (dynamic) { L.copy(b.owner[0], nullptr, 4 * N); L.copy(a.npick, nullptr, 4 * N); }      // 0x7f7f7f7f > any query index; 0
     L.copy(a.flags, nullptr, 16);                                   // collision, changed: 0
@@ -332,14 +325,17 @@ void engine_layout(Layout &L, SearchArgs &a, EngineBufs &b, int n, int nq, int n
     if (dq) dq->regions(L);
     b.down = L.results();
     if (dynamic) L.take(b.owner[1], 4 * N);                         // scratch behind the results: not copied back
+    if (on_device) { L.take(b.q, Q * sizeof(SivoSearchQuery)); L.take(a.qdesc, 32 * Q); L.take(a.blocked, N); }
 }
 
+}  // namespace
+
 // The engine on host arrays: upload queries, rounds, finalize, download.  With `dq` the queries come from the device and `queries` is
-// not read; without it nothing of the layout or the launches changes.
+// not read; without it nothing of the layout or the launches changes.  (declared in search_engine.hpp)
 void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *query_desc, int nq, const int32_t *cand_begin,
                 const int32_t *cand_end, const int32_t *cand_idx, int n_cand, const SivoSearchRule &rule, const uint8_t *blocked,
                 int32_t *match_query, int32_t *match_train, int32_t *best_dist, int32_t *second_dist, int *n_matches,
-                int *rounds_out, DeviceQueries *dq = nullptr) {
+                int *rounds_out, DeviceQueries *dq) {
     if (rounds_out) *rounds_out = 0;
     if (n_matches) *n_matches = 0;
     if (match_train) for (int k = 0; k < F.n; ++k) match_train[k] = -1;
@@ -369,11 +365,11 @@ void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *q
     }
     std::memset(L.host(a.flags), 0, 16);
     L.send(st);
-    if (dq) dq->launch(F, b.q);
+    if (dq) dq->launch(F, EngineRegions{b.q, const_cast<uint4 *>(a.qdesc), const_cast<uint8_t *>(a.blocked)});
 
     a.V = F.view();
     a.nq = nq; a.q = b.q; a.rule = rule;
-    if (!blocked) a.blocked = nullptr;
+    if (!blocked && !(dq && dq->device_inputs())) a.blocked = nullptr;
     int rounds = 0;
     for (;; ++rounds) {
         a.owner_prev = rounds == 0 ? nullptr : b.owner[(rounds + 1) & 1];
@@ -410,6 +406,8 @@ void run_search(sivo_mframe &F, const SivoSearchQuery *queries, const uint8_t *q
     if (dq) dq->collect(L);
 }
 
+namespace {
+
 // Frame::GetFeaturesInArea (Frame.cc:326-390) on the host copy of the grid.
 void features_in_area(const sivo_mframe &F, float x, float y, float r, int minLevel, int maxLevel, std::vector<int32_t> &out) {
     out.clear();
@@ -435,6 +433,8 @@ void level_range(int minLevel, int maxLevel, int32_t &lo, int32_t &hi) {
     hi = maxLevel >= 0 ? maxLevel : INT_MAX;
 }
 
+}  // namespace
+
 SivoSearchRule make_rule(int th, int gate_mode, int ratio_mode, float nn, bool ori, bool dynamic) {
     SivoSearchRule r;
     std::memset(&r, 0, sizeof r);
@@ -442,6 +442,8 @@ SivoSearchRule make_rule(int th, int gate_mode, int ratio_mode, float nn, bool o
     r.check_orientation = ori ? 1 : 0; r.dynamic = dynamic ? 1 : 0;
     return r;
 }
+
+namespace {
 
 void require(bool ok, const char *what) {
     if (!ok) throw std::invalid_argument(what);
@@ -504,9 +506,9 @@ struct LocalPointQueries : DeviceQueries {
         if (skip) L.copy(a.skip, skip, N);
         L.take(a.status, N); L.take(a.px, 4 * N); L.take(a.py, 4 * N); L.take(a.pxr, 4 * N); L.take(a.vc, 4 * N); L.take(a.level, 4 * N);
     }
-    void launch(const sivo_mframe &F, SivoSearchQuery *d_q) override {
+    void launch(const sivo_mframe &F, const EngineRegions &r) override {
         a.scale = F.view().scale;                                  // (after scratch(): the frame may have moved to a bigger slab)
-        a.q = d_q;
+        a.q = r.q;
         hipLaunchKernelGGL(fr_queries_kernel, dim3((unsigned)cdiv((int)N, 256)), dim3(256), 0, F.stream, a);
         SIVO_HIP(hipGetLastError());
     }

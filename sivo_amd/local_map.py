@@ -1,6 +1,8 @@
 """The tracking thread's local map on a map that stays on the device: Tracking::UpdateLocalMap (reference src/orbslam/Tracking.cc:1087-1235)
 — the vote, mvpLocalKeyFrames, mpReferenceKF and mvpLocalMapPoints — per frame, on tables uploaded once (sivo_amd/csrc/localmap.hip).
-Host numpy arrays in and out.  Integer results: exact, in the reference's order."""
+Host numpy arrays in and out.  Integer results: exact, in the reference's order.  The handle also keeps the map points' attributes
+(set_points / get_points), so that search_local_points runs the update and Tracking::SearchLocalPoints (:1033-1085) in one call
+(sivo_amd/csrc/localmap_track.hip)."""
 import ctypes as C
 
 import numpy as np
@@ -45,6 +47,16 @@ class Result:
     def __init__(self, voted, slot_cleared, local_kf, ref_kf, local_points, counts):
         self.voted, self.slot_cleared, self.local_kf, self.ref_kf = voted, slot_cleared, local_kf, ref_kf
         self.local_points, self.counts = local_points, counts
+
+
+class TrackResult(Result):
+    """What search_local_points leaves: the update's Result, and per local point status (SIVO_FRUSTUM_*), in_view, proj_x, proj_y,
+    proj_xr, view_cos, level (the last five written for the points in view only), per keypoint match (the position in local_points of
+    the matched point, or -1), and n_to_match, n_matches."""
+
+    def __init__(self, update, **search):
+        super().__init__(update.voted, update.slot_cleared, update.local_kf, update.ref_kf, update.local_points, update.counts)
+        self.__dict__.update(search)
 
 
 class WindowCapacity(SivoError):
@@ -151,6 +163,15 @@ class LocalMap:
         whose mnTrackReferenceForFrame already equals the frame's id; prev_local_kf: the local keyframes the caller holds.  The capacities
         default to what no result can exceed.  `out` (slot_cleared, local_kf, local_point, counts: arrays of the capacities' sizes) lets
         a caller see which entries the call wrote."""
+        fp, kp, pp, prev, kcap, pcap, cleared, local_kf, local_point, counts = self._update_args(
+            frame_point, kf_premarked, point_premarked, prev_local_kf, kf_capacity, point_capacity, out)
+        voted, n_kf, ref, n_pts = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        check(lib().sivo_localmap_update(self._h, len(fp), _p(fp), len(kp), _p(kp), len(pp), _p(pp), len(prev), _p(prev), C.byref(voted),
+                                         _p(cleared), kcap, _p(local_kf), C.byref(n_kf), C.byref(ref), pcap, _p(local_point), C.byref(n_pts),
+                                         _p(counts)))
+        return Result(bool(voted.value), cleared, local_kf[:n_kf.value] if voted.value else None, int(ref.value), local_point[:n_pts.value], counts)
+
+    def _update_args(self, frame_point, kf_premarked, point_premarked, prev_local_kf, kf_capacity, point_capacity, out):
         fp = _a(frame_point, np.int32)
         kp = _a(() if kf_premarked is None else kf_premarked, np.int32)
         pp = _a(() if point_premarked is None else point_premarked, np.int32)
@@ -161,18 +182,72 @@ class LocalMap:
         pcap = min(self.n_points, g_max) if point_capacity is None else int(point_capacity)
         out = out or {}
         cleared = out.get("slot_cleared", np.zeros(len(fp), np.uint8))
-        local_kf = out.get("local_kf", np.zeros(kcap, np.int32))
-        local_point = out.get("local_point", np.zeros(pcap, np.int32))
+        local_kf = out.get("local_kf", np.zeros(max(kcap, 0), np.int32))
+        local_point = out.get("local_point", np.zeros(max(pcap, 0), np.int32))
         counts = out.get("counts", np.zeros(self.n_kf, np.int32))
         for name, arr, n, dt in (("slot_cleared", cleared, len(fp), np.uint8), ("local_kf", local_kf, kcap, np.int32),
                                  ("local_point", local_point, pcap, np.int32), ("counts", counts, self.n_kf, np.int32)):
             if arr.dtype != dt or arr.ndim != 1 or len(arr) < n or not arr.flags.c_contiguous:
                 raise ValueError("out[%r] must be a contiguous %s array of at least %d entries" % (name, np.dtype(dt).name, n))
-        voted, n_kf, ref, n_pts = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
-        check(lib().sivo_localmap_update(self._h, len(fp), _p(fp), len(kp), _p(kp), len(pp), _p(pp), len(prev), _p(prev), C.byref(voted),
-                                         _p(cleared), kcap, _p(local_kf), C.byref(n_kf), C.byref(ref), pcap, _p(local_point), C.byref(n_pts),
-                                         _p(counts)))
-        return Result(bool(voted.value), cleared, local_kf[:n_kf.value] if voted.value else None, int(ref.value), local_point[:n_pts.value], counts)
+        return fp, kp, pp, prev, kcap, pcap, cleared, local_kf, local_point, counts
+
+    @staticmethod
+    def _rows(idx, pos, normal, min_dist, max_dist, desc, n_obs):
+        idx = _a(idx, np.int32); n = len(idx)
+        rows = (_a(pos, np.float32), _a(normal, np.float32), _a(min_dist, np.float32), _a(max_dist, np.float32), _a(desc, np.uint8),
+                _a(n_obs, np.int32))
+        for x, per in zip(rows, (3, 3, 1, 1, 32, 1)):
+            if len(x) != per * n:
+                raise ValueError("the attribute arrays must hold one row per index")
+        return (idx,) + rows
+
+    def set_points(self, idx, pos, normal, min_dist, max_dist, desc, n_obs):
+        """The attributes of the listed points (idx strictly increasing): pos = mWorldPos and normal = mNormalVector (n, 3) float32,
+        min_dist / max_dist = mfMinDistance / mfMaxDistance raw, desc = GetDescriptor() (n, 32) uint8, n_obs = Observations().  One
+        upload and a scatter on the device; the rows stay over apply(), and replace() unsets them all."""
+        idx, pos, normal, lo, hi, desc, n_obs = self._rows(idx, pos, normal, min_dist, max_dist, desc, n_obs)
+        check(lib().sivo_localmap_set_points(self._h, len(idx), _p(idx), _p(pos), _p(normal), _p(lo), _p(hi), _p(desc), _p(n_obs)))
+
+    def get_points(self, idx):
+        """The stored rows of the listed points (idx strictly increasing): a dict of pos, normal, min_dist, max_dist, desc, n_obs and
+        is_set; a row nobody set reads as zeros."""
+        idx = _a(idx, np.int32); n = len(idx)
+        r = dict(pos=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3), np.float32), min_dist=np.zeros(n, np.float32),
+                 max_dist=np.zeros(n, np.float32), desc=np.zeros((n, 32), np.uint8), n_obs=np.zeros(n, np.int32), is_set=np.zeros(n, np.uint8))
+        check(lib().sivo_localmap_get_points(self._h, n, _p(idx), *[r[k].ctypes.data for k in
+                                                                     ("pos", "normal", "min_dist", "max_dist", "desc", "n_obs", "is_set")]))
+        r["is_set"] = r["is_set"].astype(bool)
+        return r
+
+    def search_local_points(self, frame, frustum, frame_point, kf_premarked=None, point_premarked=None, prev_local_kf=(), seen_point=(),
+                            th=1.0, nn_ratio=0.8, *, kf_capacity=None, point_capacity=None, out=None):
+        """update() and Tracking::SearchLocalPoints in one call (sivo_localmap_search_local_points).  frame: a matcher.MatchFrame with as
+        many keys as frame_point has slots; frustum: tracking.frustum(...); seen_point: the points whose mnLastFrameSeen already equals
+        the frame's id and that the frame does not hold.  Every point of the handle must have its attributes (set_points).  `out` may
+        also hold status, proj_x, proj_y, proj_xr, view_cos, level (of the point capacity's size) and match: contiguous arrays of
+        the documented types are written in place.  Returns a TrackResult."""
+        fp, kp, pp, prev, kcap, pcap, cleared, local_kf, local_point, counts = self._update_args(
+            frame_point, kf_premarked, point_premarked, prev_local_kf, kf_capacity, point_capacity, out)
+        seen = _a(seen_point, np.int32)
+        out = out or {}
+        n = max(pcap, 0)
+        per_point = {k: (np.zeros(n, dt) if k not in out else np.ascontiguousarray(out[k], dt))
+                     for k, dt in (("status", np.uint8), ("proj_x", np.float32), ("proj_y", np.float32), ("proj_xr", np.float32),
+                                   ("view_cos", np.float32), ("level", np.int32))}
+        match = np.zeros(len(fp), np.int32) if "match" not in out else np.ascontiguousarray(out["match"], np.int32)
+        if any(len(v) < n for v in per_point.values()) or len(match) < len(fp):
+            raise ValueError("a search output is shorter than its capacity")
+        voted, n_kf, ref, n_pts, nt, nm = (C.c_int32(-1) for _ in range(6))
+        check(lib().sivo_localmap_search_local_points(
+            self._h, frame._h, C.byref(frustum), len(fp), _p(fp), len(kp), _p(kp), len(pp), _p(pp), len(prev), _p(prev), len(seen), _p(seen),
+            th, nn_ratio, C.byref(voted), _p(cleared), kcap, _p(local_kf), C.byref(n_kf), C.byref(ref), pcap, _p(local_point), C.byref(n_pts),
+            _p(counts), *[_p(per_point[k]) for k in ("status", "proj_x", "proj_y", "proj_xr", "view_cos", "level")], _p(match),
+            C.byref(nt), C.byref(nm)))
+        upd = Result(bool(voted.value), cleared, local_kf[:n_kf.value] if voted.value else None, int(ref.value), local_point[:n_pts.value], counts)
+        k = n_pts.value
+        search = {name: v[:k] for name, v in per_point.items()}
+        return TrackResult(upd, in_view=per_point["status"][:k] == 0, match=match, n_to_match=nt.value, n_matches=nm.value, full=per_point,
+                           **search)
 
     def ba_window(self, cand_kf, kf_local_premarked=None, kf_fixed_premarked=None, point_premarked=None, *, kf_capacity=None,
                   point_capacity=None, edge_capacity=None):
